@@ -9,8 +9,12 @@ GPU (weak scaling), synthetic MV/residual/flow already resident in HBM.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  The `roofline` object is for the
 dominant hand-written kernel, the generator forward, timed with HIP events on its stream inside
-the timed region; the `cpu_baseline` object is the CPU oracle (a port of the reference's CPU
-path, validated against it by tests/golden) timed on this box's host cores, rank 0, N=1 only.
+the timed region.  A plain run sets up, warms up, times the steps and prints the line; --full adds
+the measurements that take work of their own after the timed region: the clean host cost per step,
+the classifier-convolution roofline, the generator spans of a graph-replayed run, the
+prepare_inputs sub-line and the `cpu_baseline` object, the CPU oracle (a port of the reference's
+CPU path, validated against it by tests/golden) timed on this box's host cores, rank 0, N=1 only.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -49,6 +53,30 @@ def measured_traffic(px):
     if rec.get("kernel_source_sha16") != sha:
         return None, "%s was measured on another version of gen_tiny.hip / gen_x3.hip / gen_fused.hip (stale, not reported)" % TRAFFIC_JSON
     return int(rec["gen_fwd_bytes_per_px"] * px), "%s: %s; kernel source sha16 %s" % (TRAFFIC_JSON, rec["method"], sha)
+
+
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``arrays`` (name -> tensor: what the last timed step returned) as ``out_dir/<name>.npy``, float64 tensors in float64,
+    every other one in float32.  At most DUMP_LIMIT_BYTES in all: smallest first, an array is written whole while it fits an
+    even share of what is left, else as a sample of its flattened elements drawn with a fixed seed (the same arguments give
+    the same indices, so two builds compare file by file)."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for left, name in zip(range(len(host), 0, -1), sorted(host, key=lambda k: host[k].nbytes)):
+        a = host[name]
+        keep = min(a.size, budget // left // a.itemsize)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        budget -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def usable_cores():
@@ -181,15 +209,16 @@ def classifier_conv_roofline(conv_spans, n_frames, conv_arith, hw=224):
 
 def add_rank_spread(comm, world, dev, ms_per_step, exposed_ms, host_clean_ms):
     """The per-rank part of the ``comm`` object (every --config prints the same keys): step time, exposed wait and clean host
-    cost of every rank, the host cores they share, the device."""
-    mine = torch.tensor([ms_per_step, exposed_ms or 0.0, host_clean_ms], device=dev, dtype=torch.float64)
+    cost of every rank (``host_clean_ms`` None: not measured, a run without --full), the host cores they share, the device."""
+    mine = torch.tensor([ms_per_step, exposed_ms or 0.0, host_clean_ms or 0.0], device=dev, dtype=torch.float64)
     every = [torch.zeros_like(mine) for _ in range(world)]
     dist.all_gather(every, mine)
     comm["ms_per_step_by_rank"] = [round(float(t[0]), 3) for t in every]
     comm["ms_per_step_rank_min"] = round(min(float(t[0]) for t in every), 3)
     comm["ms_per_step_rank_max"] = round(max(float(t[0]) for t in every), 3)
     comm["exposed_wait_ms_per_step_rank_max"] = round(max(float(t[1]) for t in every), 4)
-    comm["host_clean_ms_per_step_by_rank"] = [round(float(t[2]), 3) for t in every]
+    if host_clean_ms is not None:
+        comm["host_clean_ms_per_step_by_rank"] = [round(float(t[2]), 3) for t in every]
     comm["host_cores_usable"] = usable_cores()
     comm["device_of_rank0"] = torch.cuda.get_device_name(dev)
     return comm
@@ -238,7 +267,8 @@ def bench_i3d(args, rank, world, dev):
             sdata.copy_(data); starget.copy_(target)
             data, target = sdata, starget
             graph_note = ("hipGraph replay of forward + losses + backward per phase kind (%d graphs), policy / exchange / Adam eager; "
-                          "kernels_ms from HIP events in 6 eager micro-steps run right after the timed region" % len(trainer._graphs))
+                          % len(trainer._graphs) + ("kernels_ms from HIP events in 6 eager micro-steps run right after the timed region"
+                                                    if args.full else "no kernels_ms (events cannot be recorded inside a replay; --full)"))
     for _ in range(args.warmup):
         one()
     from dmcnet_amd import train as _train
@@ -252,34 +282,38 @@ def bench_i3d(args, rank, world, dev):
     ops.profile_mark()                               # brackets the timed region in a rocprofv3 trace (tools/rocprof_region.py)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, losses, _ = one()
+        logits, losses, _ = one()
     ops.profile_mark()
     host_ms = (time.perf_counter() - t0) / args.steps * 1e3      # host time to ENQUEUE a step (~ ms_per_step: launch-bound)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = elapsed_rank = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict({"output": logits}, **{"loss%d" % i: l for i, l in enumerate(losses)}))
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax)
-    if args.graph:                                   # events cannot be recorded inside a replay: eager micro-steps for the spans
+    if args.graph and args.full:                     # events cannot be recorded inside a replay: eager micro-steps for the spans
         ops.PROBE = probe                            # (with a probe installed the trainer runs a micro-step eagerly)
         for _ in range(6):
             one()
         torch.cuda.synchronize()
     ops.PROBE = None
     spans = probe.summary()
-    clean = []                                       # clean host cost: each micro-step enqueued on an empty queue (see main())
-    for _ in range(7):
+    host_clean_ms = None
+    if args.full:
+        clean = []                                   # clean host cost: each micro-step enqueued on an empty queue (see main())
+        for _ in range(7):
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            one()
+            clean.append((time.perf_counter() - t1) * 1e3)
         torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t1 = time.perf_counter()
-        one()
-        clean.append((time.perf_counter() - t1) * 1e3)
-    torch.cuda.synchronize()
-    host_clean_ms = sorted(clean)[len(clean) // 2]
+        host_clean_ms = sorted(clean)[len(clean) // 2]
     comm = {"backend": None, "world_size": 1, "note": "single process: no gradient exchange"}
     if world > 1:
         comm = trainer.comm_summary()
@@ -292,13 +326,19 @@ def bench_i3d(args, rank, world, dev):
         dist.destroy_process_group()
         return
     px = b * args.clip_length * 224 * 224
-    fwd_ms = spans["gen_tiny_fwd"][0]
-    tf = px * GEN_FLOP_PER_PX / (fwd_ms * 1e-3) / 1e12
-    print(json.dumps({
+    roofline = None                                  # graph replay without --full: no spans were recorded
+    if "gen_tiny_fwd" in spans:
+        fwd_ms = spans["gen_tiny_fwd"][0]
+        tf = px * GEN_FLOP_PER_PX / (fwd_ms * 1e-3) / 1e12
+        roofline = {"kernel": "dmc_gen_tiny_fwd (%d frames)" % (b * args.clip_length), "bound": "mfma",
+                    "achieved": round(tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(tf / FP32_PEAK_TFLOPS, 4), "traffic": None, "launch_ms": round(fwd_ms, 4)}
+    line = {
         "metric": "clips/sec (%d-frame 224x224 clips) dmcnet_I3D train micro-step" % args.clip_length,
         "value": round(world * b * args.steps / elapsed, 3), "unit": "clips/sec", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "host_enqueue_ms_per_step": round(host_ms, 3), "host_clean_ms_per_step": round(host_clean_ms, 3),
+        "host_enqueue_ms_per_step": round(host_ms, 3),
+        "host_clean_ms_per_step": None if host_clean_ms is None else round(host_clean_ms, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16 trunk / f32 generator",
         "data": "synthetic",
         "config": {"workload": "dmcnet_I3D HMDB-51, DenseNetTiny generator per frame + I3D trunk + Discriminator, "
@@ -306,10 +346,9 @@ def bench_i3d(args, rank, world, dev):
                                "policy (stage 1), iter_size 1" % (b, args.clip_length),
                    "global_batch": world * b, "parallelism": "dp%d" % world,
                    "final_losses": [round(float(l), 5) for l in losses]},
-        "roofline": {"kernel": "dmc_gen_tiny_fwd (%d frames)" % (b * args.clip_length), "bound": "mfma",
-                     "achieved": round(tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(tf / FP32_PEAK_TFLOPS, 4), "traffic": None, "launch_ms": round(fwd_ms, 4)},
-        "kernels_ms": {k: round(v[0], 4) for k, v in spans.items()}, "comm": comm, "launch": graph_note}))
+        "roofline": roofline,
+        "kernels_ms": {k: round(v[0], 4) for k, v in spans.items()}, "comm": comm, "launch": graph_note}
+    print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()
 
@@ -323,7 +362,14 @@ def main():
     ap.add_argument("--num-class", type=int, default=51)
     ap.add_argument("--config", default="dmcnet", choices=["dmcnet", "gan", "i3d"])
     ap.add_argument("--clip-length", type=int, default=64, help="frames per clip (i3d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the clean host cost per step, the classifier-convolution roofline, "
+                         "the generator spans of a graph-replayed run, the prepare_inputs sub-line and the CPU baseline; "
+                         "default: only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0; float32 / float64, at most "
+                         "%d MiB in all: a larger output is cut to a fixed seeded sample)" % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--miopen-find", type=int, default=1,
                     help="1 (default) = cudnn.benchmark as the reference's train.py:118 sets it: MIOpen "
                          "picks solvers by search, answered from the find-db shipped in "
@@ -469,14 +515,16 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if graphs is not None:                           # kernel durations: eager steps right after the timed replays
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if torch.is_tensor(v)})
+    if graphs is not None and args.full:             # kernel durations: eager steps right after the timed replays
         ops.PROBE = probe
         for i in range(6):
             one(i)
         torch.cuda.synchronize()
     ops.PROBE = None
     conv_spans = None
-    if args.own_conv and not gan and world == 1:
+    if args.full and args.own_conv and not gan and world == 1:
         # classifier convolutions (the step's dominant kernel family): HIP-event spans around their C-ABI calls in 7
         # extra steps right AFTER the timed region (57 spans per step would cost the timed steps ~2 %)
         per_step = []
@@ -493,16 +541,18 @@ def main():
     # the figure holds no queue back-pressure -- host_enqueue_ms_per_step above is read while the queue is full and mostly
     # measures the GPU.  With N ranks every rank does this at the same time (a barrier in front): the ranks contend for the
     # host's cores exactly as in the timed region.
-    clean = []
-    for i in range(9):
+    host_clean_ms = None
+    if args.full:
+        clean = []
+        for i in range(9):
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            one(i)
+            clean.append((time.perf_counter() - t1) * 1e3)
         torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t1 = time.perf_counter()
-        one(i)
-        clean.append((time.perf_counter() - t1) * 1e3)
-    torch.cuda.synchronize()
-    host_clean_ms = sorted(clean)[len(clean) // 2]
+        host_clean_ms = sorted(clean)[len(clean) // 2]
     comm = {"backend": None, "world_size": 1, "note": "single process: no gradient exchange"}
     if world > 1:
         # self-diagnosing multi-GPU line: which communicator, what travelled, how much of it was exposed, rank spread
@@ -528,17 +578,31 @@ def main():
     if rank == 0:
         n_frames = args.batch * S
         px = n_frames * 224 * 224
-        fwd_ms, _ = spans["gen_tiny_fwd"]
-        tf = px * GEN_FLOP_PER_PX / (fwd_ms * 1e-3) / 1e12
-        gbs = px * GEN_BYTES_PER_PX / (fwd_ms * 1e-3) / 1e9
-        traffic, traffic_src = measured_traffic(px)
+        roofline = None                              # graph replay without --full: no spans were recorded
+        if "gen_tiny_fwd" in spans:
+            fwd_ms, _ = spans["gen_tiny_fwd"]
+            tf = px * GEN_FLOP_PER_PX / (fwd_ms * 1e-3) / 1e12
+            gbs = px * GEN_BYTES_PER_PX / (fwd_ms * 1e-3) / 1e9
+            traffic, traffic_src = measured_traffic(px)
+            roofline = {
+                "kernel": "dmc_gen_tiny_fwd (EstimatorDenseNetTiny forward, %d frames)" % n_frames,
+                # the fused fp32 generator is FMA-bound (325 FLOP/B >> ridge 20 FLOP/B): the binding
+                # roof is the fp32 vector/matrix peak, reported in the "mfma" slot of the schema
+                "bound": "mfma", "achieved": round(tf, 3), "peak": FP32_PEAK_TFLOPS,
+                "unit": "TFLOP/s", "frac": round(tf / FP32_PEAK_TFLOPS, 4), "traffic": traffic,
+                "launch_ms": round(fwd_ms, 4),
+                "hbm": {"achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(gbs / HBM_PEAK_GBS, 5),
+                        "note": "algorithmic 28 B/px; 'traffic' = measured HBM bytes of the forward's launches",
+                        "traffic_source": traffic_src,
+                        "traffic_gbs": None if traffic is None else round(traffic / (fwd_ms * 1e-3) / 1e9, 1)}}
         line = {
             "metric": "clips/sec (3-seg 224x224) DMC-gen+ResNet-18 train step",
             "value": round(world * args.batch * args.steps / elapsed, 3), "unit": "clips/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "ms_per_step_median": round(median_ms, 3), "host_enqueue_ms_per_step": round(host_ms, 3),
-            "host_clean_ms_per_step": round(host_clean_ms, 3), "higher_is_better": True,
+            "host_clean_ms_per_step": None if host_clean_ms is None else round(host_clean_ms, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("dmcnet_GAN HMDB-51 split1 (Discriminator3, alternating D/G)" if gan else
                                     "HMDB-51 split1 dmcnet (no GAN), 3 segments, ResNet-18, DenseNetTiny "
@@ -564,28 +628,18 @@ def main():
                                             "error vs fp64 <= the fp32 MFMA's, tools/conv_x3_check.py)"
                                             if args.conv_arith else "fp32 MFMA") if args.own_conv
                                            else "PyTorch-ROCm (MIOpen fp32, NHWC, solver search)"},
-            "roofline": {
-                "kernel": "dmc_gen_tiny_fwd (EstimatorDenseNetTiny forward, %d frames)" % n_frames,
-                # the fused fp32 generator is FMA-bound (325 FLOP/B >> ridge 20 FLOP/B): the binding
-                # roof is the fp32 vector/matrix peak, reported in the "mfma" slot of the schema
-                "bound": "mfma", "achieved": round(tf, 3), "peak": FP32_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(tf / FP32_PEAK_TFLOPS, 4), "traffic": traffic,
-                "launch_ms": round(fwd_ms, 4),
-                "hbm": {"achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(gbs / HBM_PEAK_GBS, 5),
-                        "note": "algorithmic 28 B/px; 'traffic' = measured HBM bytes of the forward's launches",
-                        "traffic_source": traffic_src,
-                        "traffic_gbs": None if traffic is None else round(traffic / (fwd_ms * 1e-3) / 1e9, 1)}},
+            "roofline": roofline,
             "kernels_ms": {k: round(v[0], 4) for k, v in spans.items()},
             "roofline_classifier_convs": classifier_conv_roofline(conv_spans, n_frames, args.conv_arith),
             "comm": comm,
-            "launch": ("hipGraph replay of the captured step; roofline.launch_ms from HIP events around the same "
-                       "C-ABI call in 6 eager steps run right after the timed region") if graphs is not None else
+            "launch": ("hipGraph replay of the captured step; " + ("roofline.launch_ms from HIP events around the same "
+                       "C-ABI call in 6 eager steps run right after the timed region" if args.full else
+                       "no roofline (events cannot be recorded inside a replay; --full)")) if graphs is not None else
                       "eager (one launch per kernel); roofline.launch_ms from HIP events inside the timed region",
         }
-        if world == 1:
+        if args.full and world == 1:
             line["prepare_inputs"] = bench_prepare(dev, n_frames, 0 if gan else 16)
-        if world == 1 and not args.no_cpu_baseline and not gan:
+        if args.full and world == 1 and not args.no_cpu_baseline and not gan:
             line["cpu_baseline"] = cpu_baseline(args.batch, S, args.num_class)
         print(json.dumps(line))
     if world > 1:

@@ -9,10 +9,10 @@ tools/pmc_gen_traffic.sh $O > /dev/null 2>&1
 cp $OUT/gen_traffic.json profiles/${T}_gen_traffic.json; cp $OUT/gen_traffic.csv profiles/${T}_gen_traffic.csv
 cp $OUT/gen_traffic.json $P/${T}_gen_traffic.json; cp $OUT/gen_traffic.csv $P/${T}_gen_traffic.csv
 cd $GRAFT_REPO_ROOT
-python bench.py > $P/${T}_bench_default.json 2> $OUT/bench_default.err
-python bench.py --config gan --no-cpu-baseline > $P/${T}_bench_gan.json 2>/dev/null
-python bench.py --config i3d --no-cpu-baseline > $P/${T}_bench_i3d.json 2>/dev/null
-python bench.py --config i3d --graph 0 --no-cpu-baseline > $P/${T}_bench_i3d_eager.json 2>/dev/null
+python bench.py --full > $P/${T}_bench_default.json 2> $OUT/bench_default.err
+python bench.py --config gan --full --no-cpu-baseline > $P/${T}_bench_gan.json 2>/dev/null
+python bench.py --config i3d --full --no-cpu-baseline > $P/${T}_bench_i3d.json 2>/dev/null
+python bench.py --config i3d --graph 0 --full --no-cpu-baseline > $P/${T}_bench_i3d_eager.json 2>/dev/null
 tools/profile_region.sh $O ${T}_bench > /dev/null 2>&1
 tools/profile_region.sh $O ${T}_bench_one_stream DMC_WGRAD_STREAM=0 > /dev/null 2>&1
 BENCH_ARGS="--config gan" tools/profile_region.sh $O ${T}_bench_gan > /dev/null 2>&1

@@ -13,10 +13,10 @@ N=${2:-8}; B=${3:-2}
 shift; shift; shift
 EXTRA="$@"
 cd $GRAFT_REPO_ROOT
-python bench.py --no-cpu-baseline --batch $B --steps 20 --warmup 5 $EXTRA > $OUT/host_1rank.json 2> $OUT/host_1rank.err
+python bench.py --full --no-cpu-baseline --batch $B --steps 20 --warmup 5 $EXTRA > $OUT/host_1rank.json 2> $OUT/host_1rank.err
 run() {   # name, extra environment
   env $2 DMC_FORCE_DEVICE=0 DMC_DIST_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-      --master-addr 127.0.0.1 --master-port $3 bench.py --gpus $N --batch $B --steps 20 --warmup 5 --no-cpu-baseline $EXTRA \
+      --master-addr 127.0.0.1 --master-port $3 bench.py --gpus $N --batch $B --steps 20 --warmup 5 --full --no-cpu-baseline $EXTRA \
       > $OUT/host_${N}ranks_$1.json 2> $OUT/host_${N}ranks_$1.err
 }
 run replicas DMC_BENCH_REPLICAS=1 29611

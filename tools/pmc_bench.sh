@@ -9,7 +9,7 @@ i=0
 for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU" "GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   i=$((i+1))
   d=/tmp/pmc_bench_$i; rm -rf $d
-  DMC_WGRAD_STREAM=0 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $d -o x -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline "$@" > /dev/null 2>&1
+  DMC_WGRAD_STREAM=0 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $d -o x -- python $R/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline "$@" > /dev/null 2>&1
   python $R/tools/pmc_table.py $(find $d -name "x_counter_collection.csv" | head -1) > $OUT/pmc_bench_set$i.csv
 done
 python $R/tools/pmc_merge.py $OUT/pmc_bench_set1.csv $OUT/pmc_bench_set2.csv > $OUT/pmc_bench.csv
