@@ -142,6 +142,10 @@ SIGNATURES = {
     "dmc_unit3d_bf16_fwd": (_I, [_P] * 9 + [_I] * 10 + [_F, _F, _P]),
     "dmc_unit3d_bf16_fwd_into": (_I, [_P] * 9 + [_L] + [_I] * 10 + [_F, _F, _P]),
     "dmc_unit3d_bf16_bwd": (_I, [_P, _L] + [_P] * 11 + [_I] * 10 + [_P]),
+    "dmc_unit3d_bf16_eval_workspace_bytes": (_Z, [_I] * 9),
+    "dmc_unit3d_bf16_fwd_eval": (_I, [_P] * 6 + [_F, _P, _P, _L] + [_I] * 10 + [_P]),
+    "dmc_stem3d_bf16_eval_workspace_bytes": (_Z, [_I] * 4),
+    "dmc_stem3d_bf16_fwd_eval": (_I, [_P] * 6 + [_F, _P, _P] + [_I] * 5 + [_P]),
     "dmc_maxpool3d_tf_out_shape": (_I, [_I] * 10 + [_P] * 3),
     "dmc_maxpool3d_tf_bf16_fwd": (_I, [_P] * 3 + [_I] * 11 + [_P]),
     "dmc_maxpool3d_tf_bf16_bwd": (_I, [_P] * 3 + [_I] * 11 + [_P]),

@@ -74,14 +74,28 @@ struct C3dArgs {
     int N, D, H, W, Cin, Cout, Cp;
     int KD, KH, KW;        // odd extents; tap (kz, ky, kx) reads the pixel at offset (kz - KD/2, ky - KH/2, kx - KW/2)
     long M;                // N * D * H * W
+    // eval epilogue only (template argument EVAL): BatchNorm with running statistics as a per-channel affine map + ReLU
+    const float* scale;    // [pad_to(Cout, 128)]: gamma / sqrt(running_var + eps), zero beyond Cout
+    const float* shift;    // [pad_to(Cout, 128)]: beta - running_mean * scale, zero beyond Cout
+    long ld;               // elements between consecutive pixels of y (>= Cout, % 8 == 0)
+    int relu;
 };
+
+// eval epilogue of one output value: fma(acc, scale, shift) -- ONE fp32 rounding (the build has -ffp-contract=off, so the fused
+// form is written out) -- then the ReLU (a NaN passes); the caller rounds the result to bf16 once (nearest even)
+__device__ __forceinline__ float c3d_affine(float acc, float sc, float sh, int relu) {
+    const float v = __builtin_fmaf(acc, sc, sh);
+    return relu && v < 0.f ? 0.f : v;
+}
 
 // NS = stages of the transfer ring.  A step is 32 input channels of one tap: 2 x TM x TN MFMAs per wave (2 for the 64 x 64
 // tile), far less than a global -> LDS round trip; with two stages every step waited for its successor's transfer to land
 // (~1 us each: 108 steps = 100 us for a 3x3x3 layer of 128 channels on a 9,408-pixel map, 83 such launches per I3D
 // micro-step).  With NS stages NS - 1 steps are in flight and a step only waits for the OLDEST of them
 // (s_waitcnt vmcnt(<transfers of the NS - 2 younger steps>)).
-template <int BM, int BN, int WM, int WN, int NS>
+// EVAL = true: the eval-mode epilogue, y[m * ld + co] = bf16(relu?(fma(acc, scale[co], shift[co]))), no statistics; the
+// training instantiations (EVAL = false) discard it at compile time.
+template <int BM, int BN, int WM, int WN, int NS, bool EVAL>
 __global__ __launch_bounds__(WM * WN * 64) void conv3d_bf16_kernel(C3dArgs a) {
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -231,6 +245,27 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_bf16_kernel(C3dArgs a) {
     }
 
     // ---- epilogue: lane holds pixel column l31 of tile i, channels 8 gq + 4 khalf + e of tile j in acc[4 gq + e] ----
+    if constexpr (EVAL) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const int co = co0 + crow0 + 32 * j + 8 * gq + 4 * khalf;
+                if (co >= a.Cout) continue;
+                const float4 sc = *reinterpret_cast<const float4*>(a.scale + co), sh = *reinterpret_cast<const float4*>(a.shift + co);
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const long m = m0 + prow0 + 32 * i + l31;
+                    if (m >= a.M) continue;
+                    const unsigned h0 = f2bf(c3d_affine(acc[i][j][4 * gq + 0], sc.x, sh.x, a.relu));
+                    const unsigned h1 = f2bf(c3d_affine(acc[i][j][4 * gq + 1], sc.y, sh.y, a.relu));
+                    const unsigned h2 = f2bf(c3d_affine(acc[i][j][4 * gq + 2], sc.z, sh.z, a.relu));
+                    const unsigned h3 = f2bf(c3d_affine(acc[i][j][4 * gq + 3], sc.w, sh.w, a.relu));
+                    *reinterpret_cast<uint2*>(a.y + (unsigned long long)m * a.ld + co) = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
+                }
+            }
+        return;
+    }
     float* red = reinterpret_cast<float*>(lds);               // [WM][BN][2]
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -790,6 +825,26 @@ __global__ __launch_bounds__(256) void conv3d_pack_w2_kernel(const float* __rest
     }
 }
 
+// the eval entry's pack: conv3d_pack_w_kernel's forward layout of contiguous fp32 weights [Cout][Cin][T] (bf16-rounded master
+// weights, as in training: the BatchNorm is NOT folded into them), and in workgroup 0 the BatchNorm's affine map for the
+// epilogue, scale / shift [rows_pad] -- no extra launch, nothing read back by the host
+__global__ __launch_bounds__(256) void conv3d_pack_w_eval_kernel(const float* __restrict__ w, bf16_t* __restrict__ wp, int rows,
+                                                                 int rows_pad, int cols, int Cp, int T, BnEval bn, float* __restrict__ scale,
+                                                                 float* __restrict__ shift) {
+    if (blockIdx.x == 0)
+        for (int c = threadIdx.x; c < rows_pad; c += 256) bn_eval_affine(bn, rows, c, scale, shift);
+    const long total = (long)rows_pad * T * Cp;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % Cp);
+        const int t = (int)((i / Cp) % T);
+        const int r = (int)(i / ((long)Cp * T));
+        unsigned v = 0;
+        if (r < rows && c < cols) v = f2bf(w[((long)r * cols + c) * T + t]);
+        wp[i] = (bf16_t)v;
+        if (T == 27) wp[total + frag_index(r, t, c, Cp)] = (bf16_t)v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // 3 x 3 x 3, stride 1: PATCH-RESIDENT form (round 6).  The tap-stepping kernel above re-fetches the pixel rows of every
 // tap from L2 (27 transfers of the same data) and meets a barrier every 2 - 8 MFMAs per wave.  Here a workgroup owns
@@ -814,6 +869,8 @@ struct P3Args {
     unsigned magic_R, magic_Wp;              // floor(2^32 / d) + 1: n / d = umulhi(n, magic) for the small n used here
     int ablate;                              // -DDMC_MEASURE build only (option conv_ablate): 16 = patch transfers of chunk 0 only, 32 = one weight fragment for every tap,
                                              // 64 = one position fragment per tap, 128 = s_memtime clocks per phase written over stat_part
+    const float* scale; const float* shift;  // eval epilogue only (EVAL): as C3dArgs
+    long ld; int relu;
 };
 
 constexpr int P3_PITCH = 80;
@@ -833,8 +890,9 @@ __device__ __forceinline__ void p3_dma16(unsigned long long src, unsigned lds_by
 }
 
 // one consumer wave's share of a job: TMW position tiles (32 positions each) starting at tile i0 of the workgroup's P = 32 TM
-// positions, the 32 output channels from co0; `job` counts chunk jobs (buffer parity) and is advanced by nch
-template <int TM, int TMW>
+// positions, the 32 output channels from co0; `job` counts chunk jobs (buffer parity) and is advanced by nch.  EVAL: the
+// eval-mode epilogue (see conv3d_bf16_kernel)
+template <int TM, int TMW, bool EVAL>
 __device__ __forceinline__ void p3_consume(const P3Args& a, const char* p3_lds, int bufsz, int nch, int bx, int co0, int i0, bool active,
                                            int& job, long long (&tim)[3]) {
     [[maybe_unused]] long long tq = DMC_ABL(a.ablate & 128) ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -919,6 +977,16 @@ __device__ __forceinline__ void p3_consume(const P3Args& a, const char* p3_lds, 
         float s1[16], s2[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+        [[maybe_unused]] float sc[16], sh[16];               // EVAL: the affine map of channels 8 gq + 4 khalf + e (padded to 128: no mask)
+        if constexpr (EVAL) {
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const int co = co0 + 8 * gq + 4 * khalf;
+                const float4 s = *reinterpret_cast<const float4*>(a.scale + co), h = *reinterpret_cast<const float4*>(a.shift + co);
+                sc[4 * gq + 0] = s.x; sc[4 * gq + 1] = s.y; sc[4 * gq + 2] = s.z; sc[4 * gq + 3] = s.w;
+                sh[4 * gq + 0] = h.x; sh[4 * gq + 1] = h.y; sh[4 * gq + 2] = h.z; sh[4 * gq + 3] = h.w;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < TMW; ++i) {
             const unsigned f = (unsigned)(t * P + a.Wp + 1 + 32 * (i0 + i) + l31);
@@ -933,9 +1001,17 @@ __device__ __forceinline__ void p3_consume(const P3Args& a, const char* p3_lds, 
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 // v_cvt_pk_bf16_f32 (round to nearest even, as f2bf): one instruction per two values
-                pk[gq][0] = p3_cvt2(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
-                pk[gq][1] = p3_cvt2(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
-                if (a.stat_part && ok && co0 + 8 * gq + 4 * khalf < a.Cout) {
+                if constexpr (EVAL) {
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = c3d_affine(acc[i][4 * gq + e], sc[4 * gq + e], sh[4 * gq + e], a.relu);
+                    pk[gq][0] = p3_cvt2(v[0], v[1]);
+                    pk[gq][1] = p3_cvt2(v[2], v[3]);
+                } else {
+                    pk[gq][0] = p3_cvt2(acc[i][4 * gq + 0], acc[i][4 * gq + 1]);
+                    pk[gq][1] = p3_cvt2(acc[i][4 * gq + 2], acc[i][4 * gq + 3]);
+                }
+                if (!EVAL && a.stat_part && ok && co0 + 8 * gq + 4 * khalf < a.Cout) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float r = bf2f((e & 1) ? pk[gq][e >> 1] >> 16 : pk[gq][e >> 1] & 0xffffu);
@@ -952,11 +1028,11 @@ __device__ __forceinline__ void p3_consume(const P3Args& a, const char* p3_lds, 
                 const int co = co0 + 8 * (2 * pr + khalf);
                 if (co < a.Cout && ok) {
                     const u32x4 v = khalf ? u32x4{r0, r1, m0, m1} : u32x4{m0, m1, r0, r1};
-                    *reinterpret_cast<u32x4*>(a.y + m * a.Cout + co) = v;
+                    *reinterpret_cast<u32x4*>(a.y + m * (EVAL ? (size_t)a.ld : (size_t)a.Cout) + co) = v;
                 }
             }
         }
-        if (a.stat_part) {
+        if (!EVAL && a.stat_part) {
             // TM rows of partials per position tile bx (one per 32 positions); this wave owns rows i0 .. i0 + TMW - 1 of its
             // channels: its sums go to the first, zeros to the rest -- every (row, channel) is written exactly once
             // whichever way the job was shared among the waves
@@ -981,7 +1057,7 @@ __device__ __forceinline__ void p3_consume(const P3Args& a, const char* p3_lds, 
 
 // PERSISTENT: gridDim.x workgroups (one per CU) walk the (position tile, channel block) jobs with stride gridDim.x; the
 // loader streams the chunks of job after job, so the first chunk of the next job lands while the epilogue of this one runs.
-template <int TM>
+template <int TM, bool EVAL>
 __global__ __launch_bounds__(P3_THREADS) void conv3d_p3_kernel(P3Args a) {
     constexpr int P = 32 * TM;
     extern __shared__ __attribute__((aligned(1024))) char p3_lds[];      // two patch buffers of ni x 960 bytes
@@ -1065,10 +1141,10 @@ __global__ __launch_bounds__(P3_THREADS) void conv3d_p3_kernel(P3Args a) {
         const int bx = (slot / a.ny) * 8 + (id & 7), by = slot % a.ny;
         if (bx >= a.nx) continue;
         const int nt = min(4, (a.Cout - by * 128 + 31) / 32);
-        if (nt >= 3) p3_consume<TM, TM>(a, p3_lds, bufsz, nch, bx, by * 128 + wave * 32, 0, wave < nt, job, tim);
-        else if (nt == 2) p3_consume<TM, TM / 2>(a, p3_lds, bufsz, nch, bx, by * 128 + (wave & 1) * 32, (wave >> 1) * (TM / 2), true, job, tim);
-        else if constexpr (TM >= 4) p3_consume<TM, TM / 4>(a, p3_lds, bufsz, nch, bx, by * 128, wave * (TM / 4), true, job, tim);
-        else p3_consume<TM, TM / 2>(a, p3_lds, bufsz, nch, bx, by * 128, (wave & 1) * (TM / 2), wave < 2, job, tim);
+        if (nt >= 3) p3_consume<TM, TM, EVAL>(a, p3_lds, bufsz, nch, bx, by * 128 + wave * 32, 0, wave < nt, job, tim);
+        else if (nt == 2) p3_consume<TM, TM / 2, EVAL>(a, p3_lds, bufsz, nch, bx, by * 128 + (wave & 1) * 32, (wave >> 1) * (TM / 2), true, job, tim);
+        else if constexpr (TM >= 4) p3_consume<TM, TM / 4, EVAL>(a, p3_lds, bufsz, nch, bx, by * 128, wave * (TM / 4), true, job, tim);
+        else p3_consume<TM, TM / 2, EVAL>(a, p3_lds, bufsz, nch, bx, by * 128, (wave & 1) * (TM / 2), wave < 2, job, tim);
     }
     if (DMC_ABL(a.ablate & 128) && a.stat_part != nullptr && lane == 0) {  // measurement build: clocks per phase of this wave, over the statistics
         float* d = a.stat_part + (blockIdx.x * 4 + wave) * 4;
@@ -1099,10 +1175,12 @@ P3Plan p3_plan(int N, int D, int H, int W, int K, int Cout, int KD, int KH, int 
     return p;
 }
 
+template <bool EVAL>
 int launch_p3(const C3dArgs& a, const P3Plan& p, hipStream_t s) {
     P3Args q;
     const int T = 27;
     q.x = a.x; q.y = a.y; q.stat_part = a.stat_part;
+    q.scale = a.scale; q.shift = a.shift; q.ld = a.ld; q.relu = a.relu;
     q.wfrag = a.w + (size_t)((a.Cout + 127) / 128 * 128) * T * a.Cp;     // behind the [rows_pad][T][Cp] copy
     q.N = a.N; q.D = a.D; q.H = a.H; q.W = a.W; q.Cin = a.Cin; q.Cout = a.Cout; q.Cp = a.Cp;
     q.Wp = p.Wp; q.R = p.R; q.tiles_pp = p.tiles_pp; q.nx = p.nx; q.ny = p.ny; q.ni = p.ni;
@@ -1113,18 +1191,18 @@ int launch_p3(const C3dArgs& a, const P3Plan& p, hipStream_t s) {
     const unsigned cus = (unsigned)persistent_cus(256);                   // persistent: one workgroup per CU (a multiple of 8: XCD mapping)
     const unsigned grid = total < cus ? total : cus;
     static LdsLimit lim4, lim2;
-    hipError_t e = p.tm == 4 ? lim4.raise(reinterpret_cast<const void*>(&conv3d_p3_kernel<4>), 160 * 1024)
-                             : lim2.raise(reinterpret_cast<const void*>(&conv3d_p3_kernel<2>), 160 * 1024);
+    hipError_t e = p.tm == 4 ? lim4.raise(reinterpret_cast<const void*>(&conv3d_p3_kernel<4, EVAL>), 160 * 1024)
+                             : lim2.raise(reinterpret_cast<const void*>(&conv3d_p3_kernel<2, EVAL>), 160 * 1024);
     if (e != hipSuccess) return fail(DMC_E_LAUNCH, "conv3d_p3: dynamic LDS limit: %s", hipGetErrorString(e));
-    if (p.tm == 4) conv3d_p3_kernel<4><<<grid, P3_THREADS, p.lds, s>>>(q);
-    else conv3d_p3_kernel<2><<<grid, P3_THREADS, p.lds, s>>>(q);
+    if (p.tm == 4) conv3d_p3_kernel<4, EVAL><<<grid, P3_THREADS, p.lds, s>>>(q);
+    else conv3d_p3_kernel<2, EVAL><<<grid, P3_THREADS, p.lds, s>>>(q);
     return check_launch("conv3d_p3");
 }
 
-template <int BM, int BN, int WM, int WN, int NS>
+template <int BM, int BN, int WM, int WN, int NS, bool EVAL>
 int launch_c3d(const C3dArgs& a, hipStream_t s) {
     dim3 grid((unsigned)((a.M + BM - 1) / BM), (a.Cout + BN - 1) / BN);
-    conv3d_bf16_kernel<BM, BN, WM, WN, NS><<<grid, WM * WN * 64, 0, s>>>(a);
+    conv3d_bf16_kernel<BM, BN, WM, WN, NS, EVAL><<<grid, WM * WN * 64, 0, s>>>(a);
     return check_launch("conv3d_bf16");
 }
 
@@ -1145,19 +1223,21 @@ int c3d_block_pixels(int cout, long M) {
     return c == 4 ? 256 : c == 2 ? 64 : 128;
 }
 
+// EVAL: the eval-mode epilogue (a.scale, a.shift, a.ld, a.relu) on the same kernel choice
+template <bool EVAL>
 int launch_conv3d(const C3dArgs& a, hipStream_t s) {
     if (a.M <= 0) return DMC_OK;
     const P3Plan p3 = p3_plan(a.N, a.D, a.H, a.W, a.Cin, a.Cout, a.KD, a.KH, a.KW);
-    if (p3.tm) return launch_p3(a, p3, s);
+    if (p3.tm) return launch_p3<EVAL>(a, p3, s);
     switch (c3d_choice(a.Cout, a.M)) {
         // transfer-ring depth: 4 where every wave issues the same number of transfers and 4 stages fit the static LDS
         // (8 / 5 stages for the two small tiles: 20.11 vs 19.90 ms per I3D micro-step, three same-box pairs -- the LDS they take
         // costs resident workgroups)
-        case 0: return launch_c3d<128, 128, 2, 2, 4>(a, s);
-        case 1: return launch_c3d<128, 64, 2, 2, 4>(a, s);
-        case 2: return launch_c3d<64, 64, 2, 2, 4>(a, s);
-        case 3: return launch_c3d<128, 32, 4, 1, 2>(a, s);
-        default: return launch_c3d<256, 128, 4, 2, 2>(a, s);
+        case 0: return launch_c3d<128, 128, 2, 2, 4, EVAL>(a, s);
+        case 1: return launch_c3d<128, 64, 2, 2, 4, EVAL>(a, s);
+        case 2: return launch_c3d<64, 64, 2, 2, 4, EVAL>(a, s);
+        case 3: return launch_c3d<128, 32, 4, 1, 2, EVAL>(a, s);
+        default: return launch_c3d<256, 128, 4, 2, 2, EVAL>(a, s);
     }
 }
 
@@ -1233,7 +1313,8 @@ int dmc_conv3d_bf16_fwd(const void* x, const float* w, long w_s_co, long w_s_ci,
     a.x = (const bf16_t*)x; a.w = (const bf16_t*)wpack; a.y = (bf16_t*)y; a.stat_part = stat_partials;
     a.N = N; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Cp = Cp; a.KD = KD; a.KH = KH; a.KW = KW;
     a.M = (long)N * D * H * W;
-    return launch_conv3d(a, s);
+    a.scale = a.shift = nullptr; a.ld = Cout; a.relu = 0;
+    return launch_conv3d<false>(a, s);
 }
 
 // dx [N,D,H,W,Cin] bf16 from dy [N,D,H,W,Cout] bf16
@@ -1254,7 +1335,51 @@ int dmc_conv3d_bf16_dgrad(const void* dy, const float* w, long w_s_co, long w_s_
     a.x = (const bf16_t*)dy; a.w = (const bf16_t*)wpack; a.y = (bf16_t*)dx; a.stat_part = nullptr;
     a.N = N; a.D = D; a.H = H; a.W = W; a.Cin = Cout; a.Cout = Cin; a.Cp = Cp; a.KD = KD; a.KH = KH; a.KW = KW;
     a.M = (long)N * D * H * W;
-    return launch_conv3d(a, s);
+    a.scale = a.shift = nullptr; a.ld = Cin; a.relu = 0;
+    return launch_conv3d<false>(a, s);
+}
+
+// ---- eval mode: a whole Unit3Dpy forward with BatchNorm3d in eval mode (running statistics), one convolution launch ----
+// Replaces code/dmcnet_I3D/network/i3d.py:390-398 (Conv3d -> BatchNorm3d -> ReLU) under net.eval() + no_grad:
+// the BatchNorm is the per-channel affine map scale / shift, applied in the convolution's epilogue.
+
+// bytes of the workspace: forward-packed bf16 weights, then scale / shift [2][pad_to(Cout, 128)] floats
+size_t dmc_unit3d_bf16_eval_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int KD, int KH, int KW) {
+    (void)N; (void)D; (void)H; (void)W;
+    const size_t wp = (dmc_conv3d_bf16_wpack_bytes(Cin, Cout, KD, KH, KW) + 255) / 256 * 256;
+    return wp + 2 * (size_t)pad_to(Cout, 128) * sizeof(float);
+}
+
+// out [N,D,H,W] x out_ld bf16 (channels 0 .. Cout - 1 of each pixel written) = bf16(relu?(fma(conv3d(x, w), scale, shift)))
+int dmc_unit3d_bf16_fwd_eval(const void* x, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, void* workspace, void* out, long out_ld, int N, int D, int H, int W,
+                             int Cin, int Cout, int KD, int KH, int KW, int relu, dmc_stream_t stream) {
+    if (!x || !w || !gamma || !beta || !running_mean || !running_var || !workspace || !out)
+        return fail(DMC_E_INVALID, "dmc_unit3d_bf16_fwd_eval: null pointer");
+    if (!c3d_supported(N, D, H, W, Cin, Cout, KD, KH, KW))
+        return fail(DMC_E_INVALID, "dmc_unit3d_bf16_fwd_eval: unsupported shape N=%d D=%d H=%d W=%d Cin=%d Cout=%d k=%dx%dx%d",
+                    N, D, H, W, Cin, Cout, KD, KH, KW);
+    if (out_ld < Cout || out_ld % 8 != 0 || ((size_t)out & 15) != 0 || ((size_t)workspace & 15) != 0)
+        return fail(DMC_E_INVALID, "dmc_unit3d_bf16_fwd_eval: out_ld=%ld must be >= Cout=%d and a multiple of 8, out and workspace 16-byte aligned",
+                    out_ld, Cout);
+    hipStream_t s = (hipStream_t)stream;
+    const int T = KD * KH * KW, Cp = pad_to(Cin, 32), rows_pad = pad_to(Cout, 128);
+    const long total = (long)rows_pad * T * Cp;
+    char* ws = static_cast<char*>(workspace);
+    const size_t wp = (dmc_conv3d_bf16_wpack_bytes(Cin, Cout, KD, KH, KW) + 255) / 256 * 256;
+    float* scale = reinterpret_cast<float*>(ws + wp);
+    float* shift = scale + rows_pad;
+    BnEval bn{gamma, beta, running_mean, running_var, eps};
+    conv3d_pack_w_eval_kernel<<<(int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256), 256, 0, s>>>(
+        w, (bf16_t*)ws, Cout, rows_pad, Cin, Cp, T, bn, scale, shift);
+    int rc = check_launch("conv3d_pack_w_eval");
+    if (rc) return rc;
+    C3dArgs a;
+    a.x = (const bf16_t*)x; a.w = (const bf16_t*)ws; a.y = (bf16_t*)out; a.stat_part = nullptr;
+    a.N = N; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Cp = Cp; a.KD = KD; a.KH = KH; a.KW = KW;
+    a.M = (long)N * D * H * W;
+    a.scale = scale; a.shift = shift; a.ld = out_ld; a.relu = relu ? 1 : 0;
+    return launch_conv3d<true>(a, s);
 }
 
 // bytes of the split-K partials of the weight gradient

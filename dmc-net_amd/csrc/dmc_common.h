@@ -191,6 +191,24 @@ __device__ __forceinline__ double half32_sum_hi(double v) {
 }
 }  // namespace dmc
 
+// ---- BatchNorm with running statistics as a per-channel affine map (the eval epilogues of conv3d_bf16.hip, stem3d_bf16.hip) ----
+// scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale in fp32: each operation rounded once (division and
+// square root correctly rounded; the product and the difference are NOT fused); channels c >= C get (0, 0).  Statistics are read,
+// never written.
+namespace dmc {
+struct BnEval { const float* gamma; const float* beta; const float* mean; const float* var; float eps; };
+__device__ __forceinline__ void bn_eval_affine(const BnEval& b, int C, int c, float* scale, float* shift) {
+    float sc = 0.f, sh = 0.f;
+    if (c < C) {
+        sc = b.gamma[c] / sqrtf(b.var[c] + b.eps);
+        const float ms = b.mean[c] * sc;
+        sh = b.beta[c] - ms;
+    }
+    scale[c] = sc;
+    shift[c] = sh;
+}
+}  // namespace dmc
+
 // ---- bf16x3 slice tensors (conv_x3s.hip and their producers in bn_act.hip) -------------------------------
 // An fp32 value is the exact sum of three bf16 values: s0 = its upper 16 bits, s1 = the upper 16 bits of the exact
 // remainder, s2 = the second remainder.  A slice tensor of a [M][C] fp32 activation is bf16 [3][C / 16][M][16].

@@ -73,14 +73,35 @@ __global__ __launch_bounds__(256) void stem3d_pack_w_kernel(const float* __restr
     wp[i] = (bf16_t)v;
 }
 
+// the eval entry's pack: stem3d_pack_w_kernel, and in workgroup 0 the BatchNorm's affine map scale / shift [64] for the epilogue
+__global__ __launch_bounds__(256) void stem3d_pack_w_eval_kernel(const float* __restrict__ w, bf16_t* __restrict__ wp, BnEval bn,
+                                                                 float* __restrict__ scale, float* __restrict__ shift) {
+    if (blockIdx.x == 0 && threadIdx.x < S3_CO) bn_eval_affine(bn, S3_CO, threadIdx.x, scale, shift);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S3_KB * S3_CO * 16) return;
+    const int j = i & 15, co = (i >> 4) % S3_CO, kb = i / (16 * S3_CO);
+    unsigned v = 0;
+    if (j < 14) {
+        const int kx = j >> 1, c = j & 1;
+        v = f2bf(w[((co * 2 + c) * 343) + kb * 7 + kx]);
+    }
+    wp[i] = (bf16_t)v;
+}
+
 struct Stem3dArgs {
     const unsigned* xq;    // [N][Tp][Hp][Wp] dwords
     const bf16_t* wp;      // [49][64][16]
     bf16_t* y;             // [N][OD][OH][OW][64]
     float* stat_part;      // [gridDim.x * 8][64][2] or null
     int N, OD, OH, OW, Tp, Hp, Wp, tiles_x;
+    const float* scale;    // EVAL only: [64] gamma / sqrt(running_var + eps)
+    const float* shift;    // EVAL only: [64] beta - running_mean * scale
+    int relu;              // EVAL only
 };
 
+// EVAL = true: the eval-mode epilogue y = bf16(relu?(fma(acc, scale[co], shift[co]))) (one fp32 rounding, then one bf16 rounding,
+// nearest even), no statistics; the training instantiation (EVAL = false) discards it at compile time
+template <bool EVAL>
 __global__ __launch_bounds__(S3_WAVES * 64) void stem3d_fwd_kernel(Stem3dArgs a) {
     extern __shared__ __attribute__((aligned(16))) char wlds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -98,6 +119,17 @@ __global__ __launch_bounds__(S3_WAVES * 64) void stem3d_fwd_kernel(Stem3dArgs a)
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
         for (int e = 0; e < 16; ++e) { s1[ct][e] = 0.f; s2[ct][e] = 0.f; }
+    [[maybe_unused]] float sc[2][16], sh[2][16];           // EVAL: the affine map of this lane's channels 32 ct + 8 g + 4 half + e
+    if constexpr (EVAL) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int c = 32 * ct + 8 * (e >> 2) + 4 * half + (e & 3);
+                sc[ct][e] = a.scale[c];
+                sh[ct][e] = a.shift[c];
+            }
+    }
 
     for (long tile = (long)blockIdx.x * S3_WAVES + wave; tile < ntiles; tile += stride) {
         const int xt = (int)(tile % a.tiles_x);
@@ -153,15 +185,20 @@ __global__ __launch_bounds__(S3_WAVES * 64) void stem3d_fwd_kernel(Stem3dArgs a)
                     unsigned h[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        h[e] = f2bf(acc[ct][4 * g + e]);
-                        const float rv = bf2f(h[e]);
-                        s1[ct][4 * g + e] += rv; s2[ct][4 * g + e] += rv * rv;
+                        if constexpr (EVAL) {
+                            const float v = __builtin_fmaf(acc[ct][4 * g + e], sc[ct][4 * g + e], sh[ct][4 * g + e]);
+                            h[e] = f2bf(a.relu && v < 0.f ? 0.f : v);
+                        } else {
+                            h[e] = f2bf(acc[ct][4 * g + e]);
+                            const float rv = bf2f(h[e]);
+                            s1[ct][4 * g + e] += rv; s2[ct][4 * g + e] += rv * rv;
+                        }
                     }
                     *reinterpret_cast<u32x2*>(dst + 32 * ct + 8 * g + 4 * half) = u32x2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
                 }
         }
     }
-    if (a.stat_part) {
+    if (!EVAL && a.stat_part) {
         float* dst = a.stat_part + ((size_t)blockIdx.x * S3_WAVES + wave) * S3_CO * 2;
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
@@ -1103,12 +1140,52 @@ int dmc_stem3d_bf16_fwd(const float* x, const float* w, void* workspace, void* y
     a.xq = xq; a.wp = wp; a.y = (bf16_t*)y; a.stat_part = stat_partials;
     a.N = N; a.OD = (T + 5 - 7) / 2 + 1; a.OH = (H + 5 - 7) / 2 + 1; a.OW = (W + 5 - 7) / 2 + 1;
     a.Tp = Tp; a.Hp = Hp; a.Wp = Wp; a.tiles_x = (a.OW + 31) / 32;
+    a.scale = a.shift = nullptr; a.relu = 0;
     static LdsLimit lim_attr;
-    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&stem3d_fwd_kernel), S3_WLDS);
+    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&stem3d_fwd_kernel<false>), S3_WLDS);
     if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "stem3d: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
     const long tiles = (long)N * a.OD * a.OH * a.tiles_x;
-    stem3d_fwd_kernel<<<s3_blocks(tiles), S3_WAVES * 64, S3_WLDS, s>>>(a);
+    stem3d_fwd_kernel<false><<<s3_blocks(tiles), S3_WAVES * 64, S3_WLDS, s>>>(a);
     return check_launch("stem3d_fwd");
+}
+
+// eval mode (code/dmcnet_I3D/network/i3d.py:480-481 through :390-398 with BatchNorm3d in eval mode, under no_grad): bytes of the
+// workspace -- dmc_stem3d_bf16_fwd's, then scale / shift [2][64] floats
+size_t dmc_stem3d_bf16_eval_workspace_bytes(int N, int T, int H, int W) {
+    return (dmc_stem3d_bf16_workspace_bytes(N, T, H, W) + 255) / 256 * 256 + 2 * S3_CO * sizeof(float);
+}
+
+// y [N,OD,OH,OW,64] bf16 NDHWC (dense) = bf16(relu?(fma(conv3d(pad_SAME(x), w), scale, shift))): dmc_stem3d_bf16_fwd with the
+// BatchNorm's running statistics as a per-channel affine map in the epilogue (scale / shift computed by the pack launch)
+int dmc_stem3d_bf16_fwd_eval(const float* x, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, void* workspace, void* y, int N, int T, int H, int W, int relu,
+                             dmc_stream_t stream) {
+    if (!x || !w || !gamma || !beta || !running_mean || !running_var || !workspace || !y)
+        return fail(DMC_E_INVALID, "dmc_stem3d_bf16_fwd_eval: null pointer");
+    if (N <= 0 || T < 2 || H < 2 || W < 2) return fail(DMC_E_INVALID, "dmc_stem3d_bf16_fwd_eval: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    const int Tp = T + 5, Hp = H + 5, Wp = (W + 5 + 1 + 3) / 4 * 4;
+    unsigned* xq = (unsigned*)workspace;
+    bf16_t* wp = (bf16_t*)((char*)workspace + (size_t)N * Tp * Hp * Wp * 4);
+    float* scale = (float*)((char*)workspace + (dmc_stem3d_bf16_workspace_bytes(N, T, H, W) + 255) / 256 * 256);
+    const long total = (long)N * Tp * Hp * Wp;
+    stem3d_prep_kernel<<<(int)(total / Wp > 16384 ? 16384 : total / Wp), 256, 0, s>>>(x, xq, N, T, H, W, Tp, Hp, Wp);
+    int rc = check_launch("stem3d_prep");
+    if (rc) return rc;
+    BnEval bn{gamma, beta, running_mean, running_var, eps};
+    stem3d_pack_w_eval_kernel<<<(S3_KB * S3_CO * 16 + 255) / 256, 256, 0, s>>>(w, wp, bn, scale, scale + S3_CO);
+    if ((rc = check_launch("stem3d_pack_w_eval"))) return rc;
+    Stem3dArgs a;
+    a.xq = xq; a.wp = wp; a.y = (bf16_t*)y; a.stat_part = nullptr;
+    a.N = N; a.OD = (T + 5 - 7) / 2 + 1; a.OH = (H + 5 - 7) / 2 + 1; a.OW = (W + 5 - 7) / 2 + 1;
+    a.Tp = Tp; a.Hp = Hp; a.Wp = Wp; a.tiles_x = (a.OW + 31) / 32;
+    a.scale = scale; a.shift = scale + S3_CO; a.relu = relu ? 1 : 0;
+    static LdsLimit lim_attr;
+    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&stem3d_fwd_kernel<true>), S3_WLDS);
+    if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "stem3d: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+    const long tiles = (long)N * a.OD * a.OH * a.tiles_x;
+    stem3d_fwd_kernel<true><<<s3_blocks(tiles), S3_WAVES * 64, S3_WLDS, s>>>(a);
+    return check_launch("stem3d_fwd_eval");
 }
 
 // bytes of the weight gradient's workspace (prepared cue + partials; the larger of the two forms)

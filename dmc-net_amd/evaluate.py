@@ -5,9 +5,13 @@ Mirrors the reference's ``test.py`` (code/dmcnet/test.py:139-198: forward over
 the videos re-ordered by sorted name) and ``combine.py`` (code/dmcnet/combine.py:35-57: weighted
 sum of the I-frame / MV / residual / DMC score files, arg-max accuracy).  The forward pass is the
 training path's HIP generator + classifier in eval mode; nothing here needs a gradient.
+
+The I3D variant's video-level evaluator (``evaluate_i3d``) restates ``code/dmcnet_I3D/test/evaluate_video_{hmdb,ucf101}_i3d.py``
+and the metrics of ``code/dmcnet_I3D/train/metric.py``.
 """
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 
 @torch.no_grad()
@@ -33,6 +37,68 @@ def evaluate(model, loader, test_segments, test_crops=1, device="cuda:0"):
     pred = np.array([int(np.argmax(x[0])) for x in output])
     labels = np.array([x[1] for x in output])
     return output, float((pred == labels).mean() * 100.0) if len(output) else 0.0
+
+
+@torch.no_grad()
+def evaluate_i3d(net, loader, device, score_path=None):
+    """Video-level evaluation of the I3D variant: the loop of the reference's evaluator
+    (code/dmcnet_I3D/test/evaluate_video_hmdb_i3d.py:171-253; evaluate_video_ucf101_i3d.py is the same loop) with the metrics of
+    code/dmcnet_I3D/train/metric.py -- ``MetricList(Loss("loss-ce"), Accuracy(topk=1, "top1"), Accuracy(topk=5, "top5"))``.
+
+    ``loader``: any iterable of (data [b,7|5,T,H,W], target [b], video_subpath [b]).  Per batch, with ``net`` in eval mode and no
+    autograd: logits = net(data[:, :5]) and loss = the cross entropy over the batch (its mean) -- what ``static_model.forward``
+    computes with node='logit' (code/dmcnet_I3D/train/model.py:160-188) --, then a softmax per clip.  ``net`` is the only part
+    that needs a device; everything after it runs on the host (fp32 torch tensors, the reference's operations in its order).
+
+    The reference's quirks, kept as written:
+      * a video's score is the SUM of its clips' softmax vectors, not their mean;
+      * the loss recorded for a video is the batch-mean loss of the batch in which its FIRST clip appears;
+      * loss-ce, top-1 and top-5 are computed over VIDEOS (one entry per distinct subpath, in first-seen order);
+      * the saved ``.npz`` (``score_path``) holds PER-CLIP softmax scores ``scores`` [n_clips, C] float32 and ``labels``
+        [n_clips, 1] int64, in loader order.
+
+    Returns a dict: ``metrics`` {"loss-ce", "top1", "top5"} (fractions, as the reference logs them); per video, in first-seen
+    order, ``videos``, ``video_scores`` [n, C] (softmax sums), ``video_counts``, ``video_labels``, ``video_losses``; per clip,
+    ``scores`` and ``labels`` (the arrays of the score file)."""
+    net.eval()
+    per_video = {}                                          # subpath -> [label [1], loss (0-d), softmax sum [1, C], clip count]
+    scores, labels = [], []
+    for data, target, subpaths in loader:
+        logits = net(data[:, :5].to(device=device, dtype=torch.float32, non_blocking=True))
+        loss = F.cross_entropy(logits, target.to(device))
+        prob = torch.softmax(logits, 1).cpu()
+        target = target.cpu()
+        scores.append(prob)
+        labels.append(target.reshape(-1, 1))
+        loss = loss.cpu()
+        for i in range(prob.shape[0]):
+            v = subpaths[i]
+            if v in per_video:
+                per_video[v][2] += prob[i:i + 1]
+                per_video[v][3] += 1
+            else:
+                per_video[v] = [target[i:i + 1].clone(), loss.clone(), prob[i:i + 1].clone(), 1]
+    # metric.Loss / metric.Accuracy over the videos: python-float sums divided by the number of videos
+    n = len(per_video)
+    loss_sum, hits = 0.0, {1: 0.0, 5: 0.0}
+    for label, loss, pred, _ in per_video.values():
+        loss_sum += float(loss.numpy().sum())
+        for k in hits:
+            top = pred.topk(k, 1, True, True)[1].t()
+            hits[k] += float(top.eq(label.view(1, -1).expand_as(top)).view(-1).float().sum())
+    metrics = {"loss-ce": loss_sum / n if n else float("nan"), "top1": hits[1] / n if n else float("nan"),
+               "top5": hits[5] / n if n else float("nan")}
+    clip_scores = np.concatenate([s.numpy() for s in scores], 0) if scores else np.zeros((0, 0), np.float32)
+    clip_labels = np.concatenate([t.numpy() for t in labels], 0) if labels else np.zeros((0, 1), np.int64)
+    if score_path is not None:
+        np.savez(score_path, scores=clip_scores, labels=clip_labels)
+    vals = list(per_video.values())
+    return {"metrics": metrics, "videos": list(per_video.keys()),
+            "video_scores": np.concatenate([v[2].numpy() for v in vals], 0) if vals else np.zeros((0, 0), np.float32),
+            "video_counts": np.array([v[3] for v in vals], dtype=np.int64),
+            "video_labels": np.array([int(v[0][0]) for v in vals], dtype=np.int64),
+            "video_losses": np.array([float(v[1]) for v in vals], dtype=np.float32),
+            "scores": clip_scores, "labels": clip_labels}
 
 
 def save_scores(path, output, name_list):

@@ -28,6 +28,10 @@ BRANCH_STREAMS = _os.environ.get("DMC_I3D_BRANCH_STREAMS", "1") != "0"
 JOIN_IN_PLACE = _os.environ.get("DMC_I3D_JOIN_IN_PLACE", "1") != "0"
 #: the four data gradients of a block's input summed by one kernel (DMC_I3D_FANOUT_ADD=0: the autograd engine's three additions)
 FANOUT_ADD = _os.environ.get("DMC_I3D_FANOUT_ADD", "1") != "0"
+#: eval mode (module.eval() + no_grad) of a bf16 trunk: every unit, the stem included, is ONE convolution launch with the BatchNorm's
+#: running statistics in its epilogue (ops.conv_bn_relu3d_eval / ops.stem3d_bn_relu_eval) and the Inception blocks join in place;
+#: DMC_I3D_EVAL_FUSED=0 switches off only this dispatch (conv3d_bf16 -> stock BatchNorm3d -> ReLU, MIOpen stem, torch.cat)
+EVAL_FUSED = _os.environ.get("DMC_I3D_EVAL_FUSED", "1") != "0"
 _SIDE_STREAMS = {}
 
 
@@ -73,12 +77,16 @@ class Unit3Dpy(nn.Module):
 
     def forward(self, x, into=None):
         """``into`` (optional): a channel slice of a wider NDHWC tensor that may receive the result in place; whether it did is
-        ``result.data_ptr() == into.data_ptr()`` (only the fused training-mode op does, Mixed.forward)."""
+        ``result.data_ptr() == into.data_ptr()`` (only the fused training-mode and eval-mode ops do, Mixed.forward)."""
         c = self.conv3d
         if (OWN_CONV3D and self.pad is not None and self.use_bn and not self.squeeze and c.kernel_size == (7, 7, 7)
                 and ops.stem3d_supported(x, c, self.batch3d)):
             # the 2-channel stem: forward on the bf16 matrix cores with the BatchNorm3d statistics in its epilogue
             return ops.stem3d_bn_relu(x, c, self.batch3d, self.relu)
+        if (OWN_CONV3D and EVAL_FUSED and self.pad is not None and self.use_bn and not self.squeeze and c.kernel_size == (7, 7, 7)
+                and ops.stem3d_eval_supported(x, c, self.batch3d)):
+            # eval mode: the stem's BatchNorm3d (running statistics) and ReLU in the convolution's epilogue
+            return ops.stem3d_bn_relu_eval(x, c, self.batch3d, self.relu)
         if self.pad is not None:
             x = self.pad(x)
         own = (OWN_CONV3D and self.pad is None and c.bias is None and x.is_cuda and x.dtype == torch.bfloat16
@@ -86,6 +94,9 @@ class Unit3Dpy(nn.Module):
         if own and self.use_bn and not self.squeeze and ops.conv_bn_relu3d_supported(x, c, self.batch3d):
             # conv (batch statistics in its epilogue) -> BatchNorm3d -> ReLU as one op on the bf16 kernels
             return ops.conv_bn_relu3d(x, c, self.batch3d, self.relu, into)
+        if own and EVAL_FUSED and self.use_bn and not self.squeeze and ops.conv_bn_relu3d_eval_supported(x, c, self.batch3d):
+            # eval mode: conv -> BatchNorm3d (running statistics, an affine map in the epilogue) -> ReLU as one launch
+            return ops.conv_bn_relu3d_eval(x, c, self.batch3d, self.relu, into)
         if own:
             x = ops.conv3d_bf16(x, c.weight)            # bf16 NDHWC implicit GEMM on the matrix cores
         else:
@@ -136,9 +147,11 @@ class Mixed(nn.Module):
         own = OWN_CONV3D and x.is_cuda and x.dtype == torch.bfloat16
         # Each branch's last unit writes its channels straight into the block's output (ops.conv_bn_relu3d(..., into=slice)): no
         # torch.cat -- 9 concatenations of 4 strided copies each, 0.34 ms per micro-step on the chain between two blocks.
-        # (Only the fused training-mode op writes in place; anything else falls back to the concatenation.)
+        # (Only the fused training-mode op and, under no_grad, the eval-mode op write in place; anything else falls back to the
+        # concatenation.)
         buf, slices = None, [None] * 4
-        if own and JOIN_IN_PLACE and torch.is_grad_enabled() and x.dim() == 5 and x.is_contiguous(memory_format=torch.channels_last_3d):
+        if (own and JOIN_IN_PLACE and (torch.is_grad_enabled() or EVAL_FUSED) and x.dim() == 5
+                and x.is_contiguous(memory_format=torch.channels_last_3d)):
             widths = [u.conv3d.out_channels for _, u in self._branches()]
             if all(wd % 8 == 0 for wd in widths):
                 buf = torch.empty((x.shape[0], sum(widths)) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device,

@@ -2170,3 +2170,83 @@ def stem3d_bn_relu(x, conv, bn, relu=True):
             bn.num_batches_tracked.add_(1)
     return _Stem3dBnRelu.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
                                bool(relu))
+
+
+# ---- eval mode of the I3D trunk: BatchNorm3d with RUNNING statistics in the convolution epilogue (forward only) ----
+
+def _bn_eval_ok(bn):
+    """BatchNorm3d in eval mode with running statistics and affine fp32 parameters, no autograd (the eval entries are forward-only)."""
+    return (not torch.is_grad_enabled() and not bn.training and bn.track_running_stats and bn.affine and bn.running_mean is not None
+            and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32 and bn.running_var.dtype == torch.float32)
+
+
+def conv_bn_relu3d_eval_supported(x, conv, bn):
+    """True if conv -> BatchNorm3d (eval: running statistics) [-> ReLU] of a Unit3Dpy can run forward-only as ONE convolution
+    launch with the normalisation in its epilogue (code/dmcnet_I3D/network/i3d.py:390-398 under net.eval() + no_grad)."""
+    if not _bn_eval_ok(bn) or conv.bias is not None:
+        return False
+    return conv3d_bf16_supported(x, conv.weight, conv.stride, conv.padding)
+
+
+def conv_bn_relu3d_eval(x, conv, bn, relu=True, into=None):
+    """Forward-only relu?(bn(conv(x))) with the BatchNorm's running statistics (see conv_bn_relu3d_eval_supported): the training
+    op's convolution kernels on the same bf16-rounded weights, the BatchNorm as a per-channel affine map in their epilogue
+    (dmc_unit3d_bf16_fwd_eval) -- one read of x, one write of the result, one bf16 rounding; the running buffers are read, not
+    updated.  ``into``: a channel slice of a wider channels_last_3d bf16 tensor (an Inception block's output) that receives the
+    result in place; returns it (or a new channels_last_3d bf16 tensor)."""
+    lib = _lib.load()
+    if not (x.is_cuda and conv.weight.is_cuda and bn.running_mean.is_cuda):
+        raise _lib.DmcHipError("conv_bn_relu3d_eval runs on the HIP extension only (no CPU fallback)")
+    x = _as_cl3(x)
+    wc = conv.weight.detach()
+    if not wc.is_contiguous():
+        wc = wc.contiguous()
+    n, cin, d, h, w = x.shape
+    cout, _, kd, kh, kw = wc.shape
+    geom = (n, d, h, w, cin, cout, kd, kh, kw)
+    if into is not None:
+        ld = into.stride(4)
+        if not (into.dtype == torch.bfloat16 and tuple(into.shape) == (n, cout, d, h, w) and ld >= cout and ld % 8 == 0
+                and into.storage_offset() % 8 == 0 and into.stride() == (d * h * w * ld, 1, h * w * ld, w * ld, ld)):
+            raise ValueError("conv_bn_relu3d_eval: `into` must be a channel slice of a channels_last_3d bf16 tensor of this op's shape")
+        out = into
+    else:
+        out, ld = torch.empty((n, cout, d, h, w), dtype=torch.bfloat16, device=x.device, memory_format=_CL3), cout
+    ws = torch.empty(lib.dmc_unit3d_bf16_eval_workspace_bytes(*geom), dtype=torch.uint8, device=x.device)
+    with _span("conv3d_bf16_eval"):
+        _lib.check(lib.dmc_unit3d_bf16_fwd_eval(_lib.ptr(x), _lib.ptr(wc), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean),
+                                                _lib.ptr(bn.running_var), float(bn.eps), _lib.ptr(ws), _lib.ptr(out), ld, *geom, int(relu),
+                                                _stream()), "dmc_unit3d_bf16_fwd_eval")
+    return out
+
+
+def stem3d_eval_supported(x, conv, bn):
+    """True if the I3D stem unit (2 -> 64 channels, 7x7x7, stride 2, TF-"SAME") can run forward-only with its BatchNorm3d in eval
+    mode in the convolution's epilogue: a CUDA cue inside a bf16 autocast region, no autograd."""
+    if not (x.is_cuda and x.dim() == 5 and x.shape[1] == 2 and torch.is_autocast_enabled()
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+        return False
+    if tuple(conv.weight.shape) != (64, 2, 7, 7, 7) or tuple(conv.stride) != (2, 2, 2) or conv.bias is not None:
+        return False
+    if not _bn_eval_ok(bn):
+        return False
+    return all(int(s) >= 2 and int(s) % 2 == 0 for s in x.shape[2:])
+
+
+def stem3d_bn_relu_eval(x, conv, bn, relu=True):
+    """Forward-only relu?(bn(conv3d_1a_7x7(x))) with the BatchNorm's running statistics (dmc_stem3d_bf16_fwd_eval): the stem
+    kernel with the affine map in its epilogue; a dense channels_last_3d bf16 result."""
+    lib = _lib.load()
+    if not (x.is_cuda and conv.weight.is_cuda and bn.running_mean.is_cuda):
+        raise _lib.DmcHipError("stem3d_bn_relu_eval runs on the HIP extension only (no CPU fallback)")
+    xc = x.detach().float().contiguous()
+    wc = conv.weight.detach().float().contiguous()
+    n, _, t, h, w = xc.shape
+    od, oh, ow = (t - 2) // 2 + 1, (h - 2) // 2 + 1, (w - 2) // 2 + 1
+    out = torch.empty((n, 64, od, oh, ow), dtype=torch.bfloat16, device=x.device, memory_format=_CL3)
+    work = _floats(lib.dmc_stem3d_bf16_eval_workspace_bytes(n, t, h, w), x.device)
+    with _span("stem3d_eval"):
+        _lib.check(lib.dmc_stem3d_bf16_fwd_eval(_lib.ptr(xc), _lib.ptr(wc), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean),
+                                                _lib.ptr(bn.running_var), float(bn.eps), _lib.ptr(work), _lib.ptr(out), n, t, h, w,
+                                                int(relu), _stream()), "dmc_stem3d_bf16_fwd_eval")
+    return out

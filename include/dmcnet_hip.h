@@ -619,6 +619,18 @@ int dmc_unit3d_bf16_fwd_into(const void* x, const float* w, const float* gamma, 
 int dmc_unit3d_bf16_bwd(const void* dout, long dout_ld, const void* x, const void* y, const void* fwd_workspace, const float* gamma,
                         const float* beta, void* bwd_workspace, void* dy, void* dx, float* dw, float* dgamma, float* dbeta, int N,
                         int D, int H, int W, int Cin, int Cout, int KD, int KH, int KW, int relu, dmc_stream_t stream);
+/* A whole Unit3Dpy in EVAL mode, forward only: code/dmcnet_I3D/network/i3d.py:390-398 with BatchNorm3d in eval mode (running
+ * statistics) under no_grad.  One convolution launch (the kernels of dmc_conv3d_bf16_fwd: the same bf16-rounded master weights,
+ * NOT folded with the BatchNorm) whose epilogue applies the BatchNorm as a per-channel affine map,
+ *     out[m][co] = bf16(relu?(fma(acc, scale[co], shift[co]))),  scale = gamma / sqrt(running_var + eps),
+ *     shift = beta - running_mean * scale  (fp32; fma = one rounding; bf16 round to nearest even, once),
+ * scale / shift computed on the device by the weight-pack launch (no host synchronisation; capturable); no statistics, the
+ * running buffers are read only.  out: pixel stride out_ld elements (>= Cout, a multiple of 8, `out` 16-byte aligned: a channel
+ * slice of an Inception block's output); workspace: dmc_unit3d_bf16_eval_workspace_bytes(). */
+size_t dmc_unit3d_bf16_eval_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int KD, int KH, int KW);
+int dmc_unit3d_bf16_fwd_eval(const void* x, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, void* workspace, void* out, long out_ld, int N, int D, int H, int W,
+                             int Cin, int Cout, int KD, int KH, int KW, int relu, dmc_stream_t stream);
 
 /* ---- I3D stem: forward of conv3d_1a_7x7 on the bf16 matrix cores -----------------------------------------
  * Replaces ConstantPad3d(TF-"SAME": front 2, back 3) + nn.Conv3d(2, 64, 7, stride 2) of the stem Unit3Dpy,
@@ -632,6 +644,13 @@ size_t dmc_stem3d_bf16_workspace_bytes(int N, int T, int H, int W);
 int dmc_stem3d_bf16_stat_blocks(int N, int T, int H, int W);
 int dmc_stem3d_bf16_fwd(const float* x, const float* w, void* workspace, void* y, float* stat_partials, int N, int T, int H, int W,
                         dmc_stream_t stream);
+/* the stem unit in EVAL mode, forward only (code/dmcnet_I3D/network/i3d.py:480-481 through :390-398, BatchNorm3d with running
+ * statistics, under no_grad): dmc_stem3d_bf16_fwd with the epilogue of dmc_unit3d_bf16_fwd_eval, y dense NDHWC;
+ * workspace: dmc_stem3d_bf16_eval_workspace_bytes(). */
+size_t dmc_stem3d_bf16_eval_workspace_bytes(int N, int T, int H, int W);
+int dmc_stem3d_bf16_fwd_eval(const float* x, const float* w, const float* gamma, const float* beta, const float* running_mean,
+                             const float* running_var, float eps, void* workspace, void* y, int N, int T, int H, int W, int relu,
+                             dmc_stream_t stream);
 /* weight gradient of the same convolution: dw [64,2,7,7,7] fp32 contiguous from x (rounded to bf16 as in the forward) and
  * dy [N,OD,OH,OW,64] bf16 NDHWC; GEMM over pixels on the bf16 matrix cores (plane form for rows of up to 125 output pixels:
  * csrc/stem3d_bf16.hip, stem3d_w2_kernel), deterministic split-K reduction; workspace: dmc_stem3d_bf16_wgrad_workspace_bytes(). */
