@@ -41,6 +41,9 @@ SIGNATURES = {
     "dmc_prepare_inputs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dmc_prepare_crop_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "dmc_prepare_inputs_crop": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "dmc_prepare_views_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "dmc_prepare_inputs_views": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "dmc_prepare_interp_taps": (_I, [_I, _I, _P, _P, _P]),
     "dmc_bn_act_supported": (_I, [_I, _I]),
     "dmc_bn_act_stats_bytes": (_Z, [_I]),
     "dmc_bn_act_scratch_bytes": (_Z, [_I]),

@@ -275,6 +275,20 @@ __device__ __forceinline__ float* plane_of(const CropArgs& a, int n, int c, size
                  : a.res + ((size_t)n * 3 + (c - 4)) * OHW;
 }
 
+// Views (dmc_prepare_inputs_views): the same kernels over N = N_out outputs, each of which names its source frame
+// (ten crops of a frame = ten plans over ONE uploaded frame), and optionally hands the per-block integer flow sums
+// to the interpolation kernel instead of writing repeated block means.  The band kernel is a template over the
+// argument struct and the copy kernel has a twin for views, so that what dmc_prepare_inputs_crop launches stays the
+// code it was, instruction for instruction.
+struct ViewArgs : CropArgs {
+    const int* src_index;          // [N] source frame of output n (device), or null = n
+    int* sums;                     // [N][bh][bw][2] integer block sums (upsample_interp), or null = write the flow planes
+};
+__device__ __forceinline__ int frame_of(const CropArgs&, int n) { return n; }
+__device__ __forceinline__ int frame_of(const ViewArgs& a, int n) { return a.src_index ? a.src_index[n] : n; }
+__device__ __forceinline__ int* sums_of(const CropArgs&) { return nullptr; }
+__device__ __forceinline__ int* sums_of(const ViewArgs& a) { return a.sums; }
+
 // flow_ds_factor == 0: 4 consecutive output pixels per thread, float4 stores into the seven planes
 __global__ __launch_bounds__(256) void prepare_crop_kernel(CropArgs a) {
     __shared__ Lut lut;
@@ -301,13 +315,41 @@ __global__ __launch_bounds__(256) void prepare_crop_kernel(CropArgs a) {
     }
 }
 
+// the same over views (a second kernel and not a template over the argument struct: as a template, the CropArgs
+// instantiation came out of the compiler with a different register allocation than the kernel above)
+__global__ __launch_bounds__(256) void prepare_views_kernel(ViewArgs a) {
+    __shared__ Lut lut;
+    fill_lut(a, lut);
+    __syncthreads();
+    const int qw = (a.OW + 3) / 4;                                  // 4-pixel groups per row
+    const size_t OHW = (size_t)a.OH * a.OW;
+    const size_t total = (size_t)a.N * a.OH * qw;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {
+        const int n = (int)(g / ((size_t)a.OH * qw));
+        const int rem = (int)(g - (size_t)n * a.OH * qw);
+        const int y = rem / qw, x0 = (rem - y * qw) * 4;
+        const bool flipped = a.flip && a.flip[n];
+        const Box b = box_of(a, n);
+        int v[4][7];
+        quad_values(a, a.frames + (size_t)frame_of(a, n) * a.H0 * a.W0 * 7, b, y, x0, flipped, v);
+        const size_t pix = (size_t)y * a.OW + x0;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) {
+            const int k = c < 4 ? 0 : c - 3;
+            const float o[4] = {lut.t[k][v[0][c]], lut.t[k][v[1][c]], lut.t[k][v[2][c]], lut.t[k][v[3][c]]};
+            store_plane_quad(a, plane_of(a, n, c, OHW), pix, x0, o);
+        }
+    }
+}
+
 // flow_ds_factor > 0 (the dmcnet recipes' 16): one workgroup per (frame, band of `factor` output rows), ONE pass
 // over the source: every quad's mv / residual planes are written at once, its flow values are added to
 // the band's per-block integer sums in LDS, and after a barrier the flow planes are written from the block
 // means (ragged edge blocks divide by factor^2, as skimage.measure.block_reduce's zero padding does).
 // HBM traffic = the algorithmic 7 B per sampled source pixel + 28 B per output pixel; the earlier two-kernel
 // form read the flow channels twice and round-tripped the block means.
-__global__ __launch_bounds__(256) void prepare_crop_band_kernel(CropArgs a) {
+template <class Args>
+__global__ __launch_bounds__(256) void prepare_crop_band_kernel(Args a) {
     __shared__ Lut lut;
     extern __shared__ int bsum[];                                    // [bw][2]
     fill_lut(a, lut);
@@ -318,7 +360,7 @@ __global__ __launch_bounds__(256) void prepare_crop_band_kernel(CropArgs a) {
     const size_t OHW = (size_t)a.OH * a.OW;
     const bool flipped = a.flip && a.flip[n];
     const Box b = box_of(a, n);
-    const unsigned char* fr = a.frames + (size_t)n * a.H0 * a.W0 * 7;
+    const unsigned char* fr = a.frames + (size_t)frame_of(a, n) * a.H0 * a.W0 * 7;
     const int y_begin = by * a.factor, rows = (a.OH - y_begin < a.factor) ? a.OH - y_begin : a.factor;
     for (int g = threadIdx.x; g < rows * qw; g += 256) {
         const int y = y_begin + g / qw, x0 = (g % qw) * 4;
@@ -344,6 +386,10 @@ __global__ __launch_bounds__(256) void prepare_crop_band_kernel(CropArgs a) {
         }
     }
     __syncthreads();
+    if (int* sums = sums_of(a)) {                                    // interpolated upsampling: prepare_interp_kernel writes the flow planes
+        for (int i = threadIdx.x; i < 2 * a.bw; i += 256) sums[(size_t)blockIdx.x * 2 * a.bw + i] = bsum[i];
+        return;
+    }
     const double denom = (double)(a.factor * a.factor);
     for (int g = threadIdx.x; g < rows * qw; g += 256) {
         const int y = y_begin + g / qw, x0 = (g % qw) * 4;
@@ -361,6 +407,135 @@ __global__ __launch_bounds__(256) void prepare_crop_band_kernel(CropArgs a) {
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------
+// upsample_interp: the block means are brought back to the output size by the reference's linear interpolation,
+// code/dmcnet/dataset.py:236-246 -- scipy.interpolate.interp1d(linspace(0, 1, n), means, axis)(linspace(0, 1, n * factor)),
+// along H for every block column and then along W on that result (the means sit at the END points of the axis).
+// scipy's linear kernel, restated: idx = clip(searchsorted(x, xn, 'left'), 1, n - 1), lo = idx - 1,
+//   y = ((y[idx] - y[lo]) / (x[idx] - x[lo])) * (xn - x[lo]) + y[lo]      in fp64, every operation rounded on its own.
+// searchsorted is LEFT-sided: an xn that equals a knot takes the interval to its left, so the value there is
+// slope * dx + y_lo, not y_hi copied.  interp_tap is the one statement of the tap arithmetic: the kernel and the
+// host export dmc_prepare_interp_taps both call it.
+// ------------------------------------------------------------------------------------------
+// numpy.linspace(0, 1, n)[i]: i * (1 / (n - 1)), the last element exactly 1
+__host__ __device__ inline double interp_knot(double step, int n, int i) { return i == n - 1 ? 1.0 : (double)i * step; }
+
+struct InterpTap { int lo; double dx, t; };
+__host__ __device__ inline InterpTap interp_tap(int n, int factor, int j) {      // n >= 2 blocks, 0 <= j < n * factor
+    const double step = 1.0 / (double)(n - 1), stepn = 1.0 / (double)(n * factor - 1);
+    const double v = interp_knot(stepn, n * factor, j);
+    int a = 0, b = n;                                                // first knot >= v
+    while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (interp_knot(step, n, mid) < v) a = mid + 1; else b = mid;
+    }
+    const int idx = a < 1 ? 1 : (a > n - 1 ? n - 1 : a);
+    const double x_lo = interp_knot(step, n, idx - 1);
+    InterpTap tap;
+    tap.lo = idx - 1;
+    tap.dx = interp_knot(step, n, idx) - x_lo;
+    tap.t = v - x_lo;
+    return tap;
+}
+
+struct InterpArgs {
+    const int* sums;               // [N][bh][bw][2] integer block sums of the (flipped) flow channels
+    float* flow;                   // [N][2][OH][OW]
+    int N, OH, OW, factor, bh, bw, rb;                               // rb: output rows per workgroup
+    float std_mean;
+};
+
+// one workgroup per (output, rb rows).  The tap tables of the W axis (lo, t per pixel; dx per interval) and of the
+// workgroup's rows go to LDS; then, per H interval the rows touch (at most one more than per `factor` rows), block column
+// and channel, the lower mean and the slope of pass 1; then pass 1 for every row; then the slope of every W interval of
+// pass 2.  Hoisting the slopes costs one fp64 division per interval instead of one per value -- same operands, same
+// bits -- and leaves two LDS table reads, an fp64 multiply and add, the cast and the fp32 normalisation of the other flow
+// paths per streamed value.
+__global__ __launch_bounds__(256) void prepare_interp_kernel(InterpArgs a) {
+    extern __shared__ double interp_lds[];
+    const int XW = a.bw * a.factor, XWP = (XW + 3) & ~3, RC = 2 * a.bw;
+    double* tx = interp_lds;                                         // [XWP] (XW rounded up to 4: the tables stay 16-byte aligned)
+    int* lox = reinterpret_cast<int*>(tx + XWP);                     // [XWP]
+    double* dxi = reinterpret_cast<double*>(lox + XWP);              // [bw] (bw - 1 intervals)
+    double* yt = dxi + a.bw;                                         // [rb]
+    double* ydx = yt + a.rb;                                         // [rb]
+    double* p1 = ydx + a.rb;                                         // [rb][2][bw] pass 1 of the rows
+    double* sly = p1 + (size_t)a.rb * RC;                            // [rb][2][bw] pass 1's slope, per H interval
+    double* mlo = sly + (size_t)a.rb * RC;                           // [rb][2][bw] lower mean, per H interval ...
+    double* sl = mlo;                                                // ... and, once pass 1 is done, pass 2's slopes of the rows
+    int* ylo = reinterpret_cast<int*>(mlo + (size_t)a.rb * RC);      // [rb]
+    const int chunks = (a.OH + a.rb - 1) / a.rb;
+    const int n = blockIdx.x / chunks, y_begin = (blockIdx.x - n * chunks) * a.rb;
+    const int rows = a.OH - y_begin < a.rb ? a.OH - y_begin : a.rb;
+    for (int j = threadIdx.x; j < XW + rows; j += 256) {
+        if (j < XW) {
+            const InterpTap tap = interp_tap(a.bw, a.factor, j);
+            lox[j] = tap.lo; tx[j] = tap.t;
+            dxi[tap.lo] = tap.dx;                                    // (every interval holds at least one xn; all writers agree)
+        } else {
+            const InterpTap tap = interp_tap(a.bh, a.factor, y_begin + (j - XW));
+            ylo[j - XW] = tap.lo; yt[j - XW] = tap.t; ydx[j - XW] = tap.dx;
+        }
+    }
+    __syncthreads();
+    const double denom = (double)(a.factor * a.factor);
+    const int* s = a.sums + (size_t)n * a.bh * RC;
+    for (int i = threadIdx.x; i < rows * RC; i += 256) {             // the first row of every H interval (lo grows by <= 1 per row)
+        const int r = i / RC;
+        if (r == 0 || ylo[r] != ylo[r - 1]) {
+            const int rem = i - r * RC, c = rem / a.bw, bx = rem - c * a.bw, k = ylo[r] - ylo[0];
+            const double y_lo = (double)s[((size_t)ylo[r] * a.bw + bx) * 2 + c] / denom;
+            const double y_hi = (double)s[((size_t)(ylo[r] + 1) * a.bw + bx) * 2 + c] / denom;
+            mlo[k * RC + rem] = y_lo;
+            sly[k * RC + rem] = (y_hi - y_lo) / ydx[r];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < rows * RC; i += 256) {
+        const int r = i / RC, e = (ylo[r] - ylo[0]) * RC + (i - r * RC);
+        p1[i] = sly[e] * yt[r] + mlo[e];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < rows * RC; i += 256)
+        if (i % a.bw < a.bw - 1) sl[i] = (p1[i + 1] - p1[i]) / dxi[i % a.bw];
+    __syncthreads();
+    const int qw = (a.OW + 3) / 4;
+    const size_t OHW = (size_t)a.OH * a.OW;
+    for (int g = threadIdx.x; g < rows * 2 * qw; g += 256) {
+        const int r = g / (2 * qw), rem = g - r * 2 * qw, c = rem / qw, x0 = (rem - c * qw) * 4;
+        const double* prow = p1 + (size_t)(r * 2 + c) * a.bw;
+        const double* srow = sl + (size_t)(r * 2 + c) * a.bw;
+        float* dst = a.flow + ((size_t)n * 2 + c) * OHW + (size_t)(y_begin + r) * a.OW + x0;
+        if ((a.OW & 3) == 0) {                                       // the quad's table entries as 16-byte LDS reads (scalar ones, 4 and 8 dwords apart across the lanes, conflict)
+            const int4 l4 = *reinterpret_cast<const int4*>(lox + x0);
+            const double2 t01 = *reinterpret_cast<const double2*>(tx + x0), t23 = *reinterpret_cast<const double2*>(tx + x0 + 2);
+            const int lo[4] = {l4.x, l4.y, l4.z, l4.w};
+            const double t[4] = {t01.x, t01.y, t23.x, t23.y};
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float f = (float)(srow[lo[j]] * t[j] + prow[lo[j]]);
+                o[j] = (f / 255.0f - 0.5f) / a.std_mean;
+            }
+            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < a.OW) {
+                    const int lo = lox[x0 + j];
+                    const float f = (float)(srow[lo] * tx[x0 + j] + prow[lo]);
+                    dst[j] = (f / 255.0f - 0.5f) / a.std_mean;
+                }
+        }
+    }
+}
+
+// LDS of prepare_interp_kernel for rb rows per workgroup
+size_t interp_lds_bytes(int bw, int factor, int rb) {
+    return (size_t)((bw * factor + 3) & ~3) * 12 + (size_t)bw * 8 + (size_t)rb * 2 * bw * 24 + (size_t)rb * 20;
+}
+constexpr size_t INTERP_LDS_MAX = 48 * 1024;
 
 }  // namespace
 
@@ -420,12 +595,77 @@ int dmc_prepare_inputs_crop(const unsigned char* frames_u8, const int* boxes, co
     a.bw = flow_ds_factor ? (OW + flow_ds_factor - 1) / flow_ds_factor : 0;
     a.std_mean = std4_host[0]; a.std_r = std4_host[1]; a.std_g = std4_host[2]; a.std_b = std4_host[3];
     if (flow_ds_factor > 0) {
-        prepare_crop_band_kernel<<<N * a.bh, 256, (size_t)2 * a.bw * sizeof(int), s>>>(a);
+        prepare_crop_band_kernel<CropArgs><<<N * a.bh, 256, (size_t)2 * a.bw * sizeof(int), s>>>(a);
         return check_launch("prepare_inputs_crop_band");
     }
     const size_t want = ((size_t)N * OH * ((OW + 3) / 4) + 255) / 256;
     prepare_crop_kernel<<<(int)(want > 16384 ? 16384 : want), 256, 0, s>>>(a);
     return check_launch("prepare_inputs_crop");
+}
+
+size_t dmc_prepare_views_workspace_bytes(int N_out, int OH, int OW, int flow_ds_factor, int upsample_interp) {
+    if (!upsample_interp) return dmc_prepare_crop_workspace_bytes(N_out, OH, OW, flow_ds_factor);
+    if (N_out <= 0 || OH <= 0 || OW <= 0 || flow_ds_factor <= 0) return 16;
+    const size_t bh = (OH + flow_ds_factor - 1) / flow_ds_factor, bw = (OW + flow_ds_factor - 1) / flow_ds_factor;
+    return (size_t)N_out * 2 * bh * bw * sizeof(int) + 16;
+}
+
+int dmc_prepare_inputs_views(const unsigned char* frames_u8, const int* src_index, const int* boxes,
+                             const unsigned char* flip, float* out_flow, float* out_mv, float* out_res,
+                             void* workspace, int N_src, int N_out, int H0, int W0, int OH, int OW,
+                             int flow_ds_factor, int upsample_interp, const float* std4_host, dmc_stream_t stream) {
+    if (!frames_u8 || !out_flow || !out_mv || !out_res || !workspace || !std4_host)
+        return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: null pointer");
+    if (N_src <= 0 || N_out <= 0 || H0 <= 0 || W0 <= 0 || OH <= 0 || OW <= 0 || flow_ds_factor < 0)
+        return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: bad shape");
+    if (!src_index && N_out != N_src)
+        return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: without src_index N_out must equal N_src");
+    if (!boxes && (H0 != OH || W0 != OW))
+        return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: without boxes the frames must measure OH x OW");
+    const int f = flow_ds_factor;
+    const int bh = f ? (OH + f - 1) / f : 0, bw = f ? (OW + f - 1) / f : 0;
+    int rb = 16;
+    if (upsample_interp) {
+        if (f == 0) return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: upsample_interp needs flow_ds_factor > 0");
+        if (bh < 2 || bw < 2)
+            return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: upsample_interp needs two blocks per axis (%d x %d blocks of %d)",
+                        bh, bw, f);
+        while (rb > 1 && interp_lds_bytes(bw, f, rb) > INTERP_LDS_MAX) rb >>= 1;
+        if (interp_lds_bytes(bw, f, rb) > INTERP_LDS_MAX)
+            return fail(DMC_E_INVALID, "dmc_prepare_inputs_views: upsample_interp: output width %d exceeds the tap table", OW);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ViewArgs a;
+    a.frames = frames_u8; a.boxes = boxes; a.flip = flip; a.flow = out_flow; a.mv = out_mv; a.res = out_res;
+    a.block_mean = nullptr; a.N = N_out; a.H0 = H0; a.W0 = W0; a.OH = OH; a.OW = OW; a.factor = f;
+    a.bh = bh; a.bw = bw;
+    a.std_mean = std4_host[0]; a.std_r = std4_host[1]; a.std_g = std4_host[2]; a.std_b = std4_host[3];
+    a.src_index = src_index;
+    a.sums = upsample_interp ? static_cast<int*>(workspace) : nullptr;
+    if (f == 0) {
+        const size_t want = ((size_t)N_out * OH * ((OW + 3) / 4) + 255) / 256;
+        prepare_views_kernel<<<(int)(want > 16384 ? 16384 : want), 256, 0, s>>>(a);
+        return check_launch("prepare_inputs_views");
+    }
+    prepare_crop_band_kernel<ViewArgs><<<N_out * bh, 256, (size_t)2 * bw * sizeof(int), s>>>(a);
+    int rc = check_launch("prepare_inputs_views_band");
+    if (rc || !upsample_interp) return rc;
+    InterpArgs ia;
+    ia.sums = a.sums; ia.flow = out_flow; ia.N = N_out; ia.OH = OH; ia.OW = OW; ia.factor = f; ia.bh = bh; ia.bw = bw;
+    ia.rb = rb; ia.std_mean = std4_host[0];
+    prepare_interp_kernel<<<N_out * ((OH + rb - 1) / rb), 256, interp_lds_bytes(bw, f, rb), s>>>(ia);
+    return check_launch("prepare_inputs_views_interp");
+}
+
+int dmc_prepare_interp_taps(int n_blocks, int factor, int* lo, double* dx, double* t) {
+    if (!lo || !dx || !t) return fail(DMC_E_INVALID, "dmc_prepare_interp_taps: null pointer");
+    if (n_blocks < 2 || factor <= 0)
+        return fail(DMC_E_INVALID, "dmc_prepare_interp_taps: needs n_blocks >= 2 and factor > 0 (got %d, %d)", n_blocks, factor);
+    for (int j = 0; j < n_blocks * factor; ++j) {
+        const InterpTap tap = interp_tap(n_blocks, factor, j);
+        lo[j] = tap.lo; dx[j] = tap.dx; t[j] = tap.t;
+    }
+    return DMC_OK;
 }
 
 }  // extern "C"

@@ -241,10 +241,17 @@ class CoviarDataSet(data.Dataset):
         """The same sample for the GPU-side preparation (``ops.prepare_inputs`` / ``DevicePrep``):
         ``(frames uint8 [S,H0,W0,7] as decoded, plan int32 [8], out_size (h, w), flip bool, label)``
         (plan: transforms.geometry_plan).
-        Consumes the RNG exactly as ``__getitem__`` does; 7 B/px cross PCIe instead of 28."""
+        Consumes the RNG exactly as ``__getitem__`` does; 7 B/px cross PCIe instead of 28.
+        With the 10-crop test transform (``transforms.GroupOverSample``) the plan is ``[10, 8]`` and the flip ``bool [10]``
+        (transforms.oversample_plans): ten views of each of the S frames, which travel once."""
         from . import transforms as T
         frames, label = self._load_frames(index)
-        box, out, flip = T.geometry_plan(self._transform, frames[0].shape)
+        ts = self._transform.transforms if isinstance(self._transform, T.Compose) else [self._transform]
+        if len(ts) == 1 and isinstance(ts[0], T.GroupOverSample):
+            box, out, flip = T.oversample_plans(self._transform, frames[0].shape)
+            flip = np.asarray(flip, bool)
+        else:
+            box, out, flip = T.geometry_plan(self._transform, frames[0].shape)
         return np.ascontiguousarray(np.stack(frames)).astype(np.uint8), np.asarray(box, np.int32), out, flip, label
 
 
@@ -263,13 +270,20 @@ class RawView(data.Dataset):
 
 def collate_raw(items):
     """Batch of raw items -> (frames uint8 [B,S,H0,W0,7], plans int32 [B,8], out_size, flips uint8 [B],
-    labels int64 [B]); frames of one batch must share (H0, W0) and out_size."""
+    labels int64 [B]); frames of one batch must share (H0, W0) and out_size.  Items with K views per frame (plans [K,8],
+    flips [K]: the 10-crop transform) give plans [B,K,8] and flips [B,K]; one batch holds one kind."""
     frames = torch.from_numpy(np.stack([it[0] for it in items]))
+    shapes = {np.shape(it[1]) for it in items}
+    if len(shapes) != 1:
+        raise ValueError("collate_raw: single-view and multi-view items in one batch (plan shapes %s)" % sorted(shapes))
     boxes = torch.from_numpy(np.stack([it[1] for it in items]))
     outs = {tuple(it[2]) for it in items}
     if len(outs) != 1:
         raise ValueError("collate_raw: mixed output sizes %s" % sorted(outs))
-    flips = torch.tensor([1 if it[3] else 0 for it in items], dtype=torch.uint8)
+    if boxes.dim() == 3:
+        flips = torch.from_numpy(np.stack([np.asarray(it[3], bool) for it in items]).astype(np.uint8))
+    else:
+        flips = torch.tensor([1 if it[3] else 0 for it in items], dtype=torch.uint8)
     labels = torch.tensor([int(it[4]) for it in items], dtype=torch.int64)
     return frames, boxes, outs.pop(), flips, labels
 
@@ -278,10 +292,25 @@ class DevicePrep(object):
     """Raw batch (``collate_raw``) -> the (input_flow, input_mv, input_residual, target) batch of the
     reference's loader, computed on the GPU by ``dmc_prepare_inputs_crop``: crop, bilinear resize,
     flip with x negation, 16x16 flow blockify, /255 and normalisation
-    (code/dmcnet/transforms.py:36-139, code/dmcnet/dataset.py:215-263)."""
+    (code/dmcnet/transforms.py:36-139, code/dmcnet/dataset.py:215-263).
 
-    def __init__(self, device, flow_ds_factor=0):
+    ``upsample_interp``: the dataset's option of that name (block means interpolated, not repeated;
+    code/dmcnet/dataset.py:236-246), on the device through ``dmc_prepare_inputs_views``.  :meth:`for_dataset` reads both
+    options from a ``CoviarDataSet`` so that this path and ``__getitem__`` cannot disagree.
+
+    A batch with K views per frame (the 10-crop transform: plans [B,K,8]) gives ``[B, K*S, C, H, W]`` tensors in the
+    reference's order -- index ``(o*S + s)*2 + f`` for offset o, segment s, flip bit f, view ``2*o + f`` of segment s --
+    which is what ``evaluate.forward_video(..., test_crops=K)`` expects; every frame is uploaded once."""
+
+    def __init__(self, device, flow_ds_factor=0, upsample_interp=False):
         self.device, self.flow_ds_factor = torch.device(device), flow_ds_factor
+        self.upsample_interp = bool(upsample_interp)
+
+    @classmethod
+    def for_dataset(cls, ds, device):
+        """The preparation that matches ``ds.__getitem__`` (a ``CoviarDataSet`` or a ``SyntheticCoviarDataSet``)."""
+        factor = getattr(ds, "_flow_ds_factor", getattr(ds, "flow_ds_factor", 0))
+        return cls(device, int(factor), bool(getattr(ds, "_upsample_interp", False)))
 
     def __call__(self, raw):
         from . import ops
@@ -289,10 +318,26 @@ class DevicePrep(object):
         b, s = frames.shape[:2]
         fr = ops.u8_frames_buffer((b * s,) + tuple(frames.shape[2:]), self.device)
         fr.copy_(frames.flatten(0, 1), non_blocking=True)
+        kw = {"upsample_interp": True} if self.upsample_interp else {}
+        if boxes.dim() == 3:
+            k = int(boxes.shape[1])
+            if k % 2 or tuple(flips.shape) != (b, k):
+                raise ValueError("DevicePrep: multi-view plans must be [B,K,8] with K even (crop, mirrored crop) and flips [B,K]")
+            if not boxes.is_cuda:
+                ops.check_geometry_plans(boxes.flatten(0, 1), int(frames.shape[2]), int(frames.shape[3]), int(out[0]), int(out[1]))
+            j = torch.arange(k * s)
+            view, seg = (j // (2 * s)) * 2 + j % 2, (j // 2) % s         # output j of a video = view 2*o + f of segment s
+            src = (torch.arange(b)[:, None] * s + seg[None, :]).flatten().to(torch.int32)
+            bx = boxes[:, view.to(boxes.device)].flatten(0, 1).to(self.device, non_blocking=True)
+            fl = flips[:, view.to(flips.device)].flatten().to(self.device, non_blocking=True)
+            flow, mv, res = ops.prepare_inputs(fr, fl, self.flow_ds_factor, boxes=bx, out_size=out,
+                                               src_index=src.to(self.device, non_blocking=True), **kw)
+            shp = lambda t: t.reshape((b, k * s) + tuple(t.shape[1:]))
+            return shp(flow), shp(mv), shp(res), labels.to(self.device, non_blocking=True)
         if not boxes.is_cuda:        # host plans: refuse boxes that leave the frame (the kernel cannot truncate like numpy slicing)
             ops.check_geometry_plans(boxes, int(frames.shape[2]), int(frames.shape[3]), int(out[0]), int(out[1]))
         bx = boxes.to(self.device, non_blocking=True).repeat_interleave(s, 0)
         fl = flips.to(self.device, non_blocking=True).repeat_interleave(s, 0)
-        flow, mv, res = ops.prepare_inputs(fr, fl, self.flow_ds_factor, boxes=bx, out_size=out)
+        flow, mv, res = ops.prepare_inputs(fr, fl, self.flow_ds_factor, boxes=bx, out_size=out, **kw)
         shp = lambda t: t.reshape((b, s) + tuple(t.shape[1:]))
         return shp(flow), shp(mv), shp(res), labels.to(self.device, non_blocking=True)

@@ -24,12 +24,15 @@ def forward_video(model, input_mv, input_residual, test_segments, test_crops=1):
 
 
 @torch.no_grad()
-def evaluate(model, loader, test_segments, test_crops=1, device="cuda:0"):
+def evaluate(model, loader, test_segments, test_crops=1, device="cuda:0", prep=None):
     """Returns (output, accuracy %) with ``output`` = [(video_scores [1,C], label), ...] in loader
-    order, exactly what the reference accumulates before saving."""
+    order, exactly what the reference accumulates before saving.  ``prep`` (a ``dataset.DevicePrep``)
+    turns the loader's raw uint8 batches (``dataset.RawView`` + ``dataset.collate_raw``) into the float
+    batch on the GPU, as in ``driver.validate``; with the 10-crop transform every frame is uploaded once."""
     model.eval()
     output = []
-    for _flow, input_mv, input_residual, label in loader:
+    for batch in loader:
+        _flow, input_mv, input_residual, label = prep(batch) if prep is not None else batch
         s = forward_video(model, input_mv.to(device, non_blocking=True),
                           input_residual.to(device, non_blocking=True), test_segments, test_crops)
         for b in range(s.shape[0]):

@@ -1726,21 +1726,45 @@ def check_geometry_plans(boxes, h0, w0, oh, ow):
                          % (bad, [int(v) for v in boxes[bad]], h0, w0, oh, ow))
 
 
-def prepare_inputs(frames_u8, flip=None, flow_ds_factor=0, boxes=None, out_size=None):
+def prepare_inputs(frames_u8, flip=None, flow_ds_factor=0, boxes=None, out_size=None, *, upsample_interp=False, src_index=None):
     """uint8 [N,H0,W0,7] HWC frames (+ optional [N] flip flags, [N,8] int32 geometry plans
     (y0,x0,h,w,rh,rw,cy,cx -- see transforms.geometry_plan) and an output size) on the GPU ->
     (input_flow [N,2,H,W], input_mv [N,2,H,W], input_residual
     [N,3,H,W]) exactly as the reference's loader produces them: crop + bilinear resize
     (code/dmcnet/transforms.py:36-139), flip (:47-58), blockify / normalise
-    (code/dmcnet/dataset.py:215-263).  Without ``boxes`` / ``out_size`` the frames are taken whole."""
+    (code/dmcnet/dataset.py:215-263).  Without ``boxes`` / ``out_size`` the frames are taken whole.
+
+    ``upsample_interp``: with ``flow_ds_factor`` > 0, bring the block means back by the reference's linear interpolation
+    (code/dmcnet/dataset.py:236-246) instead of by repetition -- ``CoviarDataSet(..., upsample_interp=True)``'s flow, bit for
+    bit; needs at least two blocks on each axis (scipy refuses one, so does this).  ``src_index`` [N_out] int32: output ``n`` is
+    computed from frame ``src_index[n]``; ``flip`` and ``boxes`` then have N_out entries (the ten crops of
+    ``transforms.GroupOverSample`` are ten plans over one uploaded frame).  Host-side ``src_index`` / ``boxes`` are range-checked;
+    device-resident ones are the caller's responsibility.  With both at their defaults this is ``dmc_prepare_inputs_crop``."""
     import ctypes
     lib = _lib.load()
     if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 \
             or frames_u8.shape[-1] != 7:
         raise _lib.DmcHipError("prepare_inputs expects a CUDA uint8 tensor [N,H,W,7]")
-    n, h0, w0, _ = frames_u8.shape
+    n_src, h0, w0, _ = frames_u8.shape
     dev = frames_u8.device
     oh, ow = (h0, w0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    views = bool(upsample_interp) or src_index is not None
+    n = n_src
+    if src_index is not None:
+        if src_index.dim() != 1 or src_index.numel() == 0:
+            raise ValueError("src_index must be a non-empty [N_out] tensor")
+        n = int(src_index.numel())
+        if not src_index.is_cuda and not bool(((src_index >= 0) & (src_index < n_src)).all()):
+            raise ValueError("src_index names a frame outside 0 .. %d" % (n_src - 1))
+        src_index = src_index.to(dev, torch.int32).contiguous()
+    if upsample_interp:
+        f = int(flow_ds_factor)
+        if f <= 0:
+            raise ValueError("upsample_interp needs flow_ds_factor > 0")
+        if -(-oh // f) < 2 or -(-ow // f) < 2:
+            raise ValueError("upsample_interp needs at least two %d x %d blocks on each axis of the %d x %d output" % (f, f, oh, ow))
+    if flip is not None and views and flip.numel() != n:
+        raise ValueError("flip must have one entry per output (%d)" % n)
     # the 4-pixel path reads whole aligned dwords: it needs 16 spare bytes behind the last frame.
     # ``u8_frames_buffer`` allocates such tensors; anything else is copied once into one.
     spare = frames_u8.untyped_storage().nbytes() - frames_u8.storage_offset() - frames_u8.numel()
@@ -1765,9 +1789,17 @@ def prepare_inputs(frames_u8, flip=None, flow_ds_factor=0, boxes=None, out_size=
     flow = torch.empty((n, 2, oh, ow), dtype=torch.float32, device=dev)
     mv = torch.empty((n, 2, oh, ow), dtype=torch.float32, device=dev)
     res = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev)
-    work = _floats(lib.dmc_prepare_crop_workspace_bytes(n, oh, ow, int(flow_ds_factor)), dev)
     std = torch.tensor(_STD, dtype=torch.float64).float()
     std4 = (ctypes.c_float * 4)(float(torch.mean(std)), float(std[0]), float(std[1]), float(std[2]))
+    if views:
+        work = _floats(lib.dmc_prepare_views_workspace_bytes(n, oh, ow, int(flow_ds_factor), int(bool(upsample_interp))), dev)
+        with _span("prepare_inputs"):
+            _lib.check(lib.dmc_prepare_inputs_views(_lib.ptr(padded), _lib.ptr(src_index), _lib.ptr(boxes), _lib.ptr(flip),
+                                                    _lib.ptr(flow), _lib.ptr(mv), _lib.ptr(res), _lib.ptr(work), n_src, n, h0, w0,
+                                                    oh, ow, int(flow_ds_factor), int(bool(upsample_interp)),
+                                                    ctypes.cast(std4, ctypes.c_void_p), _stream()), "dmc_prepare_inputs_views")
+        return flow, mv, res
+    work = _floats(lib.dmc_prepare_crop_workspace_bytes(n, oh, ow, int(flow_ds_factor)), dev)
     with _span("prepare_inputs"):
         _lib.check(lib.dmc_prepare_inputs_crop(_lib.ptr(padded), _lib.ptr(boxes), _lib.ptr(flip), _lib.ptr(flow),
                                                _lib.ptr(mv), _lib.ptr(res), _lib.ptr(work), n, h0, w0, oh, ow,

@@ -187,6 +187,28 @@ def geometry_plan(transform, im_shape):
     return (box[0], box[1], box[2], box[3], rs[0], rs[1], win[0], win[1]), (win[2], win[3]), flip
 
 
+def oversample_plans(transform, im_shape):
+    """The ten plans of a :class:`GroupOverSample` (alone or as the only element of a Compose) on frames of ``im_shape``
+    (H, W[, C]): ``(plans [10][8], (out_h, out_w), flips [10])`` in the transform's own order per frame -- for each of the five
+    ``fill_fix_offset(False, ...)`` offsets the crop, then its mirror image.  With a ``scale_size`` the whole frame is resized to
+    scale x scale and the crop is a window of that image; without it the crop is a window of the frame itself (a plan that
+    copies).  Nothing random: no draws are made.  ``apply_plan`` over these plans reproduces the transform bit for bit; the ten
+    outputs of a frame are ten views of ONE uploaded frame for ``ops.prepare_inputs(..., src_index=...)``."""
+    ts = transform.transforms if isinstance(transform, Compose) else [transform]
+    if len(ts) != 1 or not isinstance(ts[0], GroupOverSample):
+        raise ValueError("oversample_plans: expected a GroupOverSample, got %r" % (transform,))
+    t = ts[0]
+    h, w = int(im_shape[0]), int(im_shape[1])
+    a, b = (t.scale_worker.size, t.scale_worker.size) if t.scale_worker is not None else (h, w)
+    ca, cb = t.crop_size
+    plans, flips = [], []
+    for oa, ob in GroupMultiScaleCrop.fill_fix_offset(False, a, b, ca, cb):
+        for flip in (False, True):
+            plans.append((0, 0, h, w, a, b, oa, ob))
+            flips.append(flip)
+    return plans, (ca, cb), flips
+
+
 def apply_plan(img, plan, out, flip):
     """The CPU evaluation of a plan (what the GPU kernel computes in uint8)."""
     y0, x0, h, w, rh, rw, cy, cx = plan

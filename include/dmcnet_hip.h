@@ -271,6 +271,32 @@ int dmc_prepare_inputs_crop(const unsigned char* frames_u8, const int* boxes, co
                             int H0, int W0, int OH, int OW, int flow_ds_factor, const float* std4_host,
                             dmc_stream_t stream);
 
+/* Views and interpolated flow upsampling: dmc_prepare_inputs_crop with two additions.
+ * src_index [N_out] int32 DEVICE array or NULL: the source frame (0 .. N_src-1) output n reads, so that several
+ * outputs -- the ten crops of GroupOverSample, code/dmcnet/transforms.py:77-114 -- are plans over ONE uploaded
+ * frame; boxes [N_out,8] and flip [N_out] stay per OUTPUT.  NULL = identity, N_out must equal N_src.
+ * upsample_interp != 0 (needs flow_ds_factor > 0 and at least two blocks on each axis; scipy refuses a single
+ * block too): the block means are brought back to OH x OW by the reference's linear interpolation
+ * (code/dmcnet/dataset.py:236-246: interp1d between linspace(0, 1, n_blocks) and linspace(0, 1, n_blocks * factor),
+ * along H and then along W, fp64, first OH x OW kept) instead of by repetition, bit-identically to
+ * CoviarDataSet(..., upsample_interp=True).__getitem__.  upsample_interp == 0 computes what
+ * dmc_prepare_inputs_crop computes.  workspace: dmc_prepare_views_workspace_bytes() bytes.
+ * Everything else (frames_u8 with its 16 spare bytes, outputs, std4_host, asynchronous on the stream, no
+ * allocation, bad arguments refused before a launch) as dmc_prepare_inputs_crop.
+ *
+ * dmc_prepare_interp_taps runs on the HOST only (no GPU needed): for one axis of n_blocks >= 2 blocks it fills
+ * lo / dx / t [n_blocks * factor] with the interval index, its width x[lo+1] - x[lo] and the offset xn - x[lo]
+ * of every upsampled position, from the same function the kernel uses; the interpolated value is
+ * ((y[lo+1] - y[lo]) / dx) * t + y[lo] in fp64 with every operation rounded on its own.  Positions that
+ * coincide with a knot use the interval to their LEFT (scipy's searchsorted side).
+ */
+size_t dmc_prepare_views_workspace_bytes(int N_out, int OH, int OW, int flow_ds_factor, int upsample_interp);
+int dmc_prepare_inputs_views(const unsigned char* frames_u8, const int* src_index, const int* boxes,
+                             const unsigned char* flip, float* out_flow, float* out_mv, float* out_res,
+                             void* workspace, int N_src, int N_out, int H0, int W0, int OH, int OW,
+                             int flow_ds_factor, int upsample_interp, const float* std4_host, dmc_stream_t stream);
+int dmc_prepare_interp_taps(int n_blocks, int factor, int* lo, double* dx, double* t);
+
 /* ---- classifier stem: BatchNorm + ReLU + MaxPool2d(3, stride 2, padding 1) fused -----------------
  * Replaces `self.maxpool(self.relu(self.bn1(x)))` of the torchvision ResNet the reference builds at
  * code/dmcnet/model.py:305 (run at :352) and its autograd.  x [N,H,W,C] fp32 NHWC (conv1 output),
