@@ -591,34 +591,45 @@ __global__ __launch_bounds__(768) void x3q_wgrad_kernel(X3qWgArgs a) {
     const int lpx = lane >> 1;
     const unsigned lhalf = (unsigned)(lane & 1) << 4;
 
-    // global byte offset of pixel (padded row g, column x) in a plane of the OUTPUT grid, or OOB
-    auto pix_off = [&](int g, int x) -> unsigned {
-        const int n = g / HP_, y = g - n * HP_ - 1;
-        return (g >= 0 && n < a.N && y >= 0 && y < a.OH && x >= 0 && x < OW_) ? (unsigned)((n * a.OH + y) * OW_ + x) * 32u + lhalf : OOB;
-    };
-    // rows of group q (padded rows [R q, R q + R)) of the four class planes -> their ring slots
-    auto issue_x = [&](int q) {
+    // Transfer addresses on the OUTPUT grid (x3s_common.h, "transfer addressing"): per lane one constant per transfer -- the four
+    // class planes of a group share it --, per step the scalar base of the group.
+    const unsigned img_bytes = (unsigned)(a.OH * OW_) * 32u;
+    unsigned xpre[G::XI], dpre[G::DI];
+#pragma unroll
+    for (int i = 0; i < G::XI; ++i) {
+        const int px = 32 * i + lpx;                                    // pixel of the R x PW range
+        const int r = px / PW, col = px - r * PW - 1;
+        xpre[i] = (col >= 0 && col < OW_) ? (unsigned)(r * OW_ + col) * 32u + lhalf : NOPIX;
+    }
+#pragma unroll
+    for (int i = 0; i < G::DI; ++i) {
+        const int p = 32 * i + lpx;                                     // pixel slot p = r OW + x of the dy tile
+        dpre[i] = p < G::NPX ? (unsigned)p * 32u + lhalf : NOPIX;
+    }
+    // rows of group q (padded rows [R q, R q + R), at position g) of the four class planes -> their ring slots
+    auto issue_x = [&](int q, const WgGroupPos& g) {
+        unsigned tbase, img_off;
+        wg_group_base(g, a.N, OW_, img_bytes, tbase, img_off);
+        unsigned voff[G::XI];
+#pragma unroll
+        for (int i = 0; i < G::XI; ++i) voff[i] = wg_lane_off(tbase, xpre[i], img_bytes);
 #pragma unroll
         for (int cls = 0; cls < 4; ++cls) {
             const int D = (cls >> 1) ? G::D1 : G::D0, xpl = (cls >> 1) ? G::XPL1 : G::XPL0;
             const int slot0 = (((q % D) + D) % D) * R;
-            const unsigned soff_x = (unsigned)(tsl * 4 * nch_in + cls * nch_in + tci * 4 + tch) * a.plane_bytes;
+            const unsigned soff_x = (unsigned)(tsl * 4 * nch_in + cls * nch_in + tci * 4 + tch) * a.plane_bytes + img_off;
             const unsigned xplane = lds0 + (unsigned)(tsl * G::SLB + G::CLS_OFF[cls] + tch * xpl * 32);
 #pragma unroll
-            for (int i = 0; i < G::XI; ++i) {
-                const int px = 32 * i + lpx;                            // pixel of the R x PW range
-                const int r = px / PW, col = px - r * PW;
-                if (px < R * PW) dma_buf16(srd_x, pix_off(R * q + r, col - 1), soff_x, xplane + (unsigned)(slot0 * PW + 32 * i) * 32u);
-            }
+            for (int i = 0; i < G::XI; ++i)
+                if (32 * i + lpx < R * PW) dma_buf16(srd_x, voff[i], soff_x, xplane + (unsigned)(slot0 * PW + 32 * i) * 32u);
         }
     };
-    auto issue_dy = [&](int s, int buf) {
+    auto issue_dy = [&](const WgGroupPos& g, int buf) {
+        unsigned tbase, img_off;
+        wg_group_base(g, a.N, OW_, img_bytes, tbase, img_off);
 #pragma unroll
-        for (int i = 0; i < G::DI; ++i) {
-            const int p = 32 * i + lpx;
-            const int r = p / OW_, x = p - r * OW_;
-            dma_buf16(srd_d, p < G::NPX ? pix_off(R * s + r, x) : OOB, soff_d, dplane + (unsigned)buf * G::DYBYTES + (unsigned)(32 * i) * 32u);
-        }
+        for (int i = 0; i < G::DI; ++i)
+            dma_buf16(srd_d, wg_lane_off(tbase, dpre[i], img_bytes), soff_d + img_off, dplane + (unsigned)buf * G::DYBYTES + (unsigned)(32 * i) * 32u);
     };
 
     f32x16 acc[3];
@@ -627,11 +638,13 @@ __global__ __launch_bounds__(768) void x3q_wgrad_kernel(X3qWgArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 
+    WgGroupPos g1 = wg_group_at(s_begin, R, HP_);
     if (s_begin < s_end) {
-        issue_x(s_begin - 1);                                            // (the py = 0 rings do not need it: harmless, overwritten by s_begin + 1)
-        issue_x(s_begin);
-        issue_dy(s_begin, 0);
+        issue_x(s_begin - 1, wg_group_prev(g1, R, HP_));                 // (the py = 0 rings do not need it: harmless, overwritten by s_begin + 1)
+        issue_x(s_begin, g1);
+        issue_dy(g1, 0);
     }
+    g1 = wg_group_next(g1, R, HP_);                                      // group s + 1 at the top of step s
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // this wave's tap row: class-row parity, row shift, ring depth; its three taps kx = 0, 1, 2: classes (py, 1) (py, 0) (py, 1)
@@ -660,8 +673,9 @@ __global__ __launch_bounds__(768) void x3q_wgrad_kernel(X3qWgArgs a) {
 #pragma unroll 1
     for (int s = s_begin; s < s_end; ++s) {
         const int buf = (s - s_begin) & 1;
-        issue_x(s + 1);                                                  // the group entering the window
-        if (s + 1 < s_end) issue_dy(s + 1, buf ^ 1);
+        issue_x(s + 1, g1);                                              // the group entering the window
+        if (s + 1 < s_end) issue_dy(g1, buf ^ 1);
+        g1 = wg_group_next(g1, R, HP_);
         const int sb = (((R * s + da) % DR) + DR) % DR;                  // ring row of step row 0 for this wave's tap row (wave-uniform)
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {

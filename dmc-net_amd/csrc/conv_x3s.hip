@@ -656,29 +656,38 @@ __global__ __launch_bounds__(768) void x3s_wgrad_kernel(X3WgArgs a) {
     const int lpx = lane >> 1;
     const unsigned lhalf = (unsigned)(lane & 1) << 4;
 
-    // global byte offset of pixel (padded row g, column x) in a plane, or OOB
-    auto pix_off = [&](int g, int x) -> unsigned {
-        const int n = g / HP, y = g - n * HP - 1;
-        return (g >= 0 && n < a.N && y >= 0 && y < a.H && x >= 0 && x < W_) ? (unsigned)((n * a.H + y) * W_ + x) * 32u + lhalf : OOB;
-    };
-    // input rows of group q (padded rows [R q, R q + R)) -> ring slots R (q mod NGRP) ..
-    auto issue_x = [&](int q) {
+    // Transfer addresses (x3s_common.h, "transfer addressing"): per lane one constant per transfer, per step the scalar base of
+    // the group.  (H + 2) % R == 0 is a rule of x3s_wgrad_plan.
+    const unsigned img_bytes = (unsigned)(a.H * W_) * 32u;
+    unsigned xpre[G::XI], dpre[G::DI];
+#pragma unroll
+    for (int i = 0; i < G::XI; ++i) {
+        const int px = 32 * i + lpx;                                // pixel of the R x PW range
+        const int r = px / PW, col = px - r * PW - 1;
+        xpre[i] = (col >= 0 && col < W_) ? (unsigned)(r * W_ + col) * 32u + lhalf : NOPIX;
+    }
+#pragma unroll
+    for (int i = 0; i < G::DI; ++i) {
+        const int p = 32 * i + lpx;                                 // pixel slot p = r W + x of the dy tile
+        dpre[i] = p < G::NPX ? (unsigned)p * 32u + lhalf : NOPIX;
+    }
+    // input rows of group q (padded rows [R q, R q + R), at position g) -> ring slots R (q mod NGRP) ..
+    auto issue_x = [&](int q, const WgGroupPos& g) {
         const int slot0 = (((q % G::NGRP) + G::NGRP) % G::NGRP) * R;
+        unsigned tbase, img_off;
+        wg_group_base(g, a.N, W_, img_bytes, tbase, img_off);
 #pragma unroll
-        for (int i = 0; i < G::XI; ++i) {
-            const int px = 32 * i + lpx;                            // pixel of the R x PW range
-            const int r = px / PW, col = px - r * PW;
-            if (px < R * PW) dma_buf16(srd_x, pix_off(R * q + r, col - 1), soff_x, xplane + (unsigned)(slot0 * PW + 32 * i) * 32u);
-        }
+        for (int i = 0; i < G::XI; ++i)
+            if (32 * i + lpx < R * PW)
+                dma_buf16(srd_x, wg_lane_off(tbase, xpre[i], img_bytes), soff_x + img_off, xplane + (unsigned)(slot0 * PW + 32 * i) * 32u);
     };
-    // dy tile of step s: pixel slot p = r W + x of padded rows R s + r
-    auto issue_dy = [&](int s, int buf) {
+    // dy tile of the step whose group is at position g
+    auto issue_dy = [&](const WgGroupPos& g, int buf) {
+        unsigned tbase, img_off;
+        wg_group_base(g, a.N, W_, img_bytes, tbase, img_off);
 #pragma unroll
-        for (int i = 0; i < G::DI; ++i) {
-            const int p = 32 * i + lpx;
-            const int r = p / W_, x = p - r * W_;
-            dma_buf16(srd_d, p < G::NPX ? pix_off(R * s + r, x) : OOB, soff_d, dplane + (unsigned)buf * G::DYBYTES + (unsigned)(32 * i) * 32u);
-        }
+        for (int i = 0; i < G::DI; ++i)
+            dma_buf16(srd_d, wg_lane_off(tbase, dpre[i], img_bytes), soff_d + img_off, dplane + (unsigned)buf * G::DYBYTES + (unsigned)(32 * i) * 32u);
     };
 
     f32x16 acc[3];
@@ -687,12 +696,15 @@ __global__ __launch_bounds__(768) void x3s_wgrad_kernel(X3WgArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 
+    WgGroupPos g1 = wg_group_at(s_begin, R, HP);
     if (s_begin < s_end) {
         // every ring row the first step can touch holds zeros or data (never uninitialised LDS: 0 x NaN pattern = NaN)
+        WgGroupPos g = wg_group_prev(g1, R, HP);
 #pragma unroll
-        for (int q = -1; q < G::LA; ++q) issue_x(s_begin + q);
-        issue_dy(s_begin, 0);
+        for (int q = -1; q < G::LA; ++q, g = wg_group_next(g, R, HP)) issue_x(s_begin + q, g);
+        issue_dy(g1, 0);
     }
+    g1 = wg_group_next(g1, R, HP);                                   // group s + 1 at the top of step s
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     lds_cptr const LB = (lds_cptr)lds_wg;
@@ -714,8 +726,9 @@ __global__ __launch_bounds__(768) void x3s_wgrad_kernel(X3WgArgs a) {
 #pragma unroll 1
     for (int s = s_begin; s < s_end; ++s) {
         const int buf = (s - s_begin) & 1;
-        issue_x(s + G::LA);                                          // the group entering the window
-        if (s + 1 < s_end) issue_dy(s + 1, buf ^ 1);
+        issue_x(s + G::LA, G::LA == 1 ? g1 : wg_group_next(g1, R, HP));   // the group entering the window
+        if (s + 1 < s_end) issue_dy(g1, buf ^ 1);
+        g1 = wg_group_next(g1, R, HP);
         const int sb = (((R * s + trow - 1) % NRING) + NRING) % NRING;   // ring row of step row 0 for this wave's tap row (wave-uniform)
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) {

@@ -55,6 +55,46 @@ __device__ __forceinline__ void tr_read2(lds_cptr p0, lds_cptr p1, u32x4& f) {  
     f[0] = ua[0]; f[1] = ua[1]; f[2] = ub[0]; f[3] = ub[1];
 }
 
+// ---- transfer addressing of the weight-gradient kernels (x3s_wgrad_kernel, x3q_wgrad_kernel) ------------------------------
+// Both walk the pixels in groups of R padded image rows (HP rows per image, HP % R == 0: a group never straddles two images).
+// A lane's pixel within the group -- its row r and its column -- is the same in every step; only the group moves, and the
+// group is wave-uniform.  So the lane keeps ONE constant per transfer, pre = (r W + col) 32 + lane half (NOPIX where the column
+// is outside the image or the slot beyond the tile), and a step adds the scalar in-image base of its group:
+//     t = ((y0 - 1) W) 32 + pre       (y0 = the group's first padded row within its image; row y0 - 1 + r of the image)
+// t grows with (row, column) and the column is in range, so "the row is an image row" is 0 <= t < H W 32 as ONE unsigned
+// compare: add, compare, select per transfer, no division.  The image's own byte offset n H W 32 goes into the scalar offset
+// of the transfer.  A group outside the tensor (q = -1 in the prologue, n >= N behind the last image) gets the base NOPIX.
+// NOPIX + any base or pre stays above every image size (an image plane is far below 2^30 bytes: plane_bytes is 32 bit).
+constexpr unsigned NOPIX = 0x40000000u;
+
+struct WgGroupPos { int n, y; };                 // padded row R q = row y of image n; carried from step to step in scalar registers
+__device__ __forceinline__ WgGroupPos wg_group_at(int q, int R, int HP) {      // one scalar division, before the step loop
+    const int g = R * q, n = g / HP;
+    WgGroupPos p;
+    p.n = __builtin_amdgcn_readfirstlane(n);
+    p.y = __builtin_amdgcn_readfirstlane(g - n * HP);
+    return p;
+}
+__device__ __forceinline__ WgGroupPos wg_group_next(WgGroupPos p, int R, int HP) {
+    p.y += R;
+    if (p.y >= HP) { p.y -= HP; ++p.n; }
+    return p;
+}
+__device__ __forceinline__ WgGroupPos wg_group_prev(WgGroupPos p, int R, int HP) {
+    p.y -= R;
+    if (p.y < 0) { p.y += HP; --p.n; }
+    return p;
+}
+// scalar parts of a group's transfers: in-image base of row y - 1 (or NOPIX) and the image's byte offset within a plane
+__device__ __forceinline__ void wg_group_base(const WgGroupPos& p, int N, int W, unsigned img_bytes, unsigned& tbase, unsigned& img_off) {
+    const bool in = p.n >= 0 && p.n < N;
+    tbase = in ? (unsigned)((p.y - 1) * W) * 32u : NOPIX;
+    img_off = in ? (unsigned)p.n * img_bytes : 0u;
+}
+__device__ __forceinline__ unsigned wg_lane_off(unsigned tbase, unsigned pre, unsigned img_bytes) {
+    const unsigned t = tbase + pre;
+    return t < img_bytes ? t : OOB;
+}
 
 // ---- v_mfma_f32_16x16x32_bf16 users (conv_small.hip, gen_x3.hip) -----------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
