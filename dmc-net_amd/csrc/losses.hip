@@ -109,10 +109,12 @@ __global__ __launch_bounds__(1024) void consensus_ce_kernel(const float* __restr
         for (int c = lane; c < C; c += 64) {
             float a = 0.f;
             for (int s = 0; s < S; ++s) a += lb[(size_t)s * C + c];
-            se += __expf(a * inv_s - mx);
+            se += expf(a * inv_s - mx);
         }
         se = __shfl(wave_sum(se), 0, 64);
-        const float lse = __logf(se) + mx;
+        // everything below stays RELATIVE to the maximum: log-sum-exp = log(se) + mx carries the rounding of |mx| (4e-6 at
+        // |x| = 80), which exp(a - lse) would turn into a relative error of every probability
+        const float log_se = logf(se), inv_se = 1.f / se;
         // a label outside [0, C) never indexes memory: the clip's loss and gradient become NaN (torch's
         // CrossEntropyLoss device-asserts instead; an asynchronous C ABI cannot raise)
         const int64_t t64 = target[b];
@@ -121,13 +123,13 @@ __global__ __launch_bounds__(1024) void consensus_ce_kernel(const float* __restr
         if (lane == 0) {
             float a = 0.f;
             for (int s = 0; s < S; ++s) a += lb[(size_t)s * C + t];
-            loss += t_ok ? lse - a * inv_s : NAN;
+            loss += t_ok ? log_se + (mx - a * inv_s) : NAN;
         }
         if (grad != nullptr) {
             for (int c = lane; c < C; c += 64) {
                 float a = 0.f;
                 for (int s = 0; s < S; ++s) a += lb[(size_t)s * C + c];
-                const float p = __expf(a * inv_s - lse);
+                const float p = expf(a * inv_s - mx) * inv_se;
                 const float g = t_ok ? (p - (c == t ? 1.f : 0.f)) * inv_n : NAN;
                 for (int s = 0; s < S; ++s) grad[((size_t)b * S + s) * C + c] = g;
             }

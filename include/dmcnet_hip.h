@@ -708,7 +708,11 @@ int dmc_stem3d_bf16_dgrad(const void* dy, const float* w, float* dx, void* works
  *                      accu_old[dst] elsewhere (the reference's two buffers + memcpy; here the caller swaps the pointers)
  *   dmc_mv_from_accu   :130-139  mv_out[y][x] = (x, y) - accu[x][y]
  *   dmc_residual       :141-175  res[y][x][c] = bgr_cur[y][x][c] - bgr_ref[src_y][src_x][c], src from `accu`
- *                      (accumulate) or (x, y) - `mv` (not): pass exactly one of the two
+ *                      (accumulate) or (x, y) - `mv` (not): pass exactly one of the two.  The source position is NOT
+ *                      range-checked (neither is the reference's loop): every `accu` entry / every (x, y) - mv must lie
+ *                      inside the frame, which holds for what dmc_mv_accu_init / dmc_mv_accumulate produce and for an mv
+ *                      plane rasterised over ZEROS (or from dmc_mv_from_accu) -- not for a plane with other values left
+ *                      in its uncovered pixels
  *   dmc_mv_gop_batch   a BATCH of accumulated chains in two launches: chain c owns the frames chain_off[c] ..
  *                      chain_off[c + 1] - 1 (in decode order), frame f the vectors frame_off[f] .. frame_off[f + 1] - 1
  *                      (device int32 arrays of n_chains + 1 / n_frames + 1 entries; owner_ws of dmc_mv_owner_bytes(n_frames,
