@@ -44,6 +44,8 @@ SIGNATURES = {
     "dmc_prepare_views_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "dmc_prepare_inputs_views": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dmc_prepare_interp_taps": (_I, [_I, _I, _P, _P, _P]),
+    "dmc_prepare_clip_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "dmc_prepare_clip": (_I, [_P, _P, _P, _P] + [_I] * 8 + [_P, _P, _P]),
     "dmc_bn_act_supported": (_I, [_I, _I]),
     "dmc_bn_act_stats_bytes": (_Z, [_I]),
     "dmc_bn_act_scratch_bytes": (_Z, [_I]),

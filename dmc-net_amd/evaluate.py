@@ -43,7 +43,7 @@ def evaluate(model, loader, test_segments, test_crops=1, device="cuda:0", prep=N
 
 
 @torch.no_grad()
-def evaluate_i3d(net, loader, device, score_path=None):
+def evaluate_i3d(net, loader, device, score_path=None, prep=None):
     """Video-level evaluation of the I3D variant: the loop of the reference's evaluator
     (code/dmcnet_I3D/test/evaluate_video_hmdb_i3d.py:171-253; evaluate_video_ucf101_i3d.py is the same loop) with the metrics of
     code/dmcnet_I3D/train/metric.py -- ``MetricList(Loss("loss-ce"), Accuracy(topk=1, "top1"), Accuracy(topk=5, "top5"))``.
@@ -52,6 +52,9 @@ def evaluate_i3d(net, loader, device, score_path=None):
     autograd: logits = net(data[:, :5]) and loss = the cross entropy over the batch (its mean) -- what ``static_model.forward``
     computes with node='logit' (code/dmcnet_I3D/train/model.py:160-188) --, then a softmax per clip.  ``net`` is the only part
     that needs a device; everything after it runs on the host (fp32 torch tensors, the reference's operations in its order).
+
+    ``prep`` (an ``i3d_data.DeviceClipPrep``): the loader yields (raw, target, video_subpath) with ``raw`` the uint8 batch of
+    ``i3d_data.collate_raw_clips``, and ``data = prep(raw)`` is computed on the device (``dmc_prepare_clip``).
 
     The reference's quirks, kept as written:
       * a video's score is the SUM of its clips' softmax vectors, not their mean;
@@ -67,6 +70,8 @@ def evaluate_i3d(net, loader, device, score_path=None):
     per_video = {}                                          # subpath -> [label [1], loss (0-d), softmax sum [1, C], clip count]
     scores, labels = [], []
     for data, target, subpaths in loader:
+        if prep is not None:
+            data = prep(data)
         logits = net(data[:, :5].to(device=device, dtype=torch.float32, non_blocking=True))
         loss = F.cross_entropy(logits, target.to(device))
         prob = torch.softmax(logits, 1).cpu()

@@ -1808,6 +1808,72 @@ def prepare_inputs(frames_u8, flip=None, flow_ds_factor=0, boxes=None, out_size=
     return flow, mv, res
 
 
+_CLIP_MEAN = (0.485, 0.456, 0.406)
+
+
+def check_clip_plans(plans, h0, w0, oh, ow):
+    """Raise ValueError unless every clip plan (y1, x1, flip) takes its OH x OW window inside the H0 x W0 clip."""
+    p = plans.to(torch.int64)
+    ok = (p[:, 0] >= 0) & (p[:, 1] >= 0) & (p[:, 0] + oh <= h0) & (p[:, 1] + ow <= w0)
+    if not bool(ok.all()):
+        bad = int((~ok).nonzero()[0])
+        raise ValueError("clip plan %d = %s leaves the %d x %d clip (output %d x %d)"
+                         % (bad, [int(v) for v in plans[bad]], h0, w0, oh, ow))
+
+
+def prepare_clip(clips_u8, plans, out_size, flow_ds_factor=0, mean=_CLIP_MEAN, std=_STD, out=None):
+    """uint8 clips [B,H0,W0,T*7] as decoded (frame t = channels 7t .. 7t+6 = flow_x flow_y mv_x mv_y res0 res1 res2) and
+    [B,3] int32 plans (y1, x1, flip) -> the fp32 batch [B,7,T,OH,OW] of the reference's I3D loader for modality 'flow+mp4',
+    bit for bit: crop, flip (flow_x / mv_x -> 256 - v as uint8), ToTensor with the truncated f x f flow block means, / 255,
+    and Normalize over the first ``len(mean)`` channels only (code/dmcnet_I3D/data/image_transforms.py:47-59,138-200,
+    video_transforms.py:23-70) -- ``dmc_prepare_clip``; see ``i3d_data.ClipTransform`` for the same chain on the CPU.
+
+    ``flow_ds_factor`` 0 or 1: no blockify.  ``plans`` on the host are range-checked (``check_clip_plans``); plans already on
+    the device are the caller's responsibility.  ``out``: a contiguous fp32 [B,7,T,OH,OW] CUDA tensor to write into (it is
+    returned), e.g. the hipGraph input buffer ``I3DTrainer.static_batch()[0]``."""
+    import ctypes
+    lib = _lib.load()
+    if not clips_u8.is_cuda or clips_u8.dtype != torch.uint8 or clips_u8.dim() != 4 or clips_u8.shape[-1] % 7 \
+            or clips_u8.shape[-1] == 0:
+        raise _lib.DmcHipError("prepare_clip expects a CUDA uint8 tensor [B,H0,W0,T*7]")
+    b, h0, w0, t7 = (int(v) for v in clips_u8.shape)
+    t = t7 // 7
+    dev = clips_u8.device
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if oh <= 0 or ow <= 0 or oh > h0 or ow > w0:
+        raise ValueError("prepare_clip: output %d x %d does not fit the %d x %d clip" % (oh, ow, h0, w0))
+    if int(flow_ds_factor) < 0:
+        raise ValueError("prepare_clip: negative flow_ds_factor")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != len(std) or len(mean) > 7:
+        raise ValueError("prepare_clip: mean and std need the same number of entries, at most 7")
+    if tuple(plans.shape) != (b, 3):
+        raise ValueError("plans must be [B,3] (y1, x1, flip)")
+    if not plans.is_cuda:
+        check_clip_plans(plans, h0, w0, oh, ow)
+    plans = plans.to(dev, torch.int32).contiguous()
+    spare = clips_u8.untyped_storage().nbytes() - clips_u8.storage_offset() - clips_u8.numel()
+    if clips_u8.is_contiguous() and spare >= 16 and clips_u8.data_ptr() % 4 == 0:
+        padded = clips_u8
+    else:
+        padded = u8_frames_buffer(clips_u8.shape, dev)
+        padded.copy_(clips_u8)
+    if out is None:
+        out = torch.empty((b, 7, t, oh, ow), dtype=torch.float32, device=dev)
+    elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (b, 7, t, oh, ow) or not out.is_contiguous() \
+            or out.device != dev:
+        raise ValueError("prepare_clip: out must be a contiguous fp32 CUDA tensor %s on %s" % ((b, 7, t, oh, ow), dev))
+    n = len(mean)
+    mean_c, std_c = (ctypes.c_float * max(n, 1))(*mean), (ctypes.c_float * max(n, 1))(*std)
+    nbytes = lib.dmc_prepare_clip_workspace_bytes(b, t, oh, ow, int(flow_ds_factor))
+    work = _floats(nbytes, dev) if nbytes else None
+    with _span("prepare_clip"):
+        _lib.check(lib.dmc_prepare_clip(_lib.ptr(padded), _lib.ptr(plans), _lib.ptr(out), _lib.ptr(work), b, t, h0, w0, oh, ow,
+                                        int(flow_ds_factor), n, ctypes.cast(mean_c, ctypes.c_void_p),
+                                        ctypes.cast(std_c, ctypes.c_void_p), _stream()), "dmc_prepare_clip")
+    return out
+
+
 # ------------------------------------------------------------------ I3D trunk: bf16 Conv3d (conv3d_bf16.hip)
 _CL3 = torch.channels_last_3d
 

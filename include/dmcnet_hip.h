@@ -297,6 +297,35 @@ int dmc_prepare_inputs_views(const unsigned char* frames_u8, const int* src_inde
                              int flow_ds_factor, int upsample_interp, const float* std4_host, dmc_stream_t stream);
 int dmc_prepare_interp_taps(int n_blocks, int factor, int* lo, double* dx, double* t);
 
+/* I3D clip preparation (modality 'flow+mp4'): the tensor side of the reference's I3D loader on the device --
+ * code/dmcnet_I3D/data/iterator_factory.py:49-56,72-77 (the chains), image_transforms.py:14-35,47-59,138-200 (Compose,
+ * Normalize, CenterCrop, RandomCrop, RandomHorizontalFlip), video_transforms.py:23-70 (ToTensor) and
+ * video_iterator.py:150-178,428-433 (how a clip is packed) -- bit for bit.  Only the random draws stay on the host.
+ * clips_u8 [B,H0,W0,T*7] uint8 as decoded, frame t in channels 7t .. 7t+6 = [flow_x flow_y mv_x mv_y res0 res1 res2],
+ * with >= 16 spare bytes behind the last clip (the records are read as aligned dwords); plans [B,3] int32 DEVICE array
+ * (y1, x1, flip): the OH x OW window at (y1, x1), mirrored along W when flip != 0; out [B,7,T,OH,OW] fp32, contiguous.
+ * The reference's quirks, kept as written:
+ *   - flip: flow_x and mv_x of every frame (channels 0::7 and 2::7) become (256 - v) cast to uint8, so 0 stays 0;
+ *   - flow_ds_factor f >= 2: the two flow channels of every frame are replaced by their f x f block means (after the flip),
+ *     ragged edge blocks zero-padded and still divided by f^2 (skimage.measure.block_reduce), the mean TRUNCATED to an
+ *     integer (it is assigned into the uint8 array): floor(sum / f^2).  video_transforms.py:46 (`is not 0 or 1`) is always
+ *     true, so f = 1 is the identity; 0 and 1 both mean "no blockify" here;
+ *   - then float / 255 (fp32, true division);
+ *   - Normalize zips over the FIRST dimension and stops at len(mean): only channels 0 .. n_norm-1 (flow_x, flow_y and
+ *     mv_x for the recipe's three means) get (v - mean[c]) / std[c]; the others stay in [0, 1].  Every operation is rounded
+ *     to fp32 on its own, no reciprocal.
+ * mean_host / std_host: HOST fp32 arrays of n_norm entries, 0 <= n_norm <= 7 (may be NULL when n_norm == 0).
+ * workspace: dmc_prepare_clip_workspace_bytes() bytes -- 0, the block sums live in LDS; NULL is accepted.
+ * Asynchronous on the stream, no allocation, no synchronisation; refused before any launch: null pointers, non-positive
+ * sizes, OH > H0, OW > W0, n_norm outside 0 .. 7, a negative factor, pointers that are not 4-byte aligned, and a factor
+ * whose single block column (lcm(4, f) pixels, or the row) does not fit the LDS.  Any T >= 1 runs: frames are chunked.
+ * Plans are not range-checked on the device (ops.check_clip_plans checks host plans).
+ */
+size_t dmc_prepare_clip_workspace_bytes(int B, int T, int OH, int OW, int flow_ds_factor);
+int dmc_prepare_clip(const unsigned char* clips_u8, const int* plans, float* out, void* workspace,
+                     int B, int T, int H0, int W0, int OH, int OW, int flow_ds_factor,
+                     int n_norm, const float* mean_host, const float* std_host, dmc_stream_t stream);
+
 /* ---- classifier stem: BatchNorm + ReLU + MaxPool2d(3, stride 2, padding 1) fused -----------------
  * Replaces `self.maxpool(self.relu(self.bn1(x)))` of the torchvision ResNet the reference builds at
  * code/dmcnet/model.py:305 (run at :352) and its autograd.  x [N,H,W,C] fp32 NHWC (conv1 output),
