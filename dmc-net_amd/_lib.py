@@ -78,6 +78,7 @@ SIGNATURES = {
     "dmc_x3s_conv_supported": (_I, [_I] * 5),
     "dmc_x3s_conv_stat_blocks": (_I, [_I] * 4),
     "dmc_x3s_conv_fwd": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "dmc_x3s_conv_bn_eval": (_I, [_P] * 8 + [_I] * 7 + [_P]),
     "dmc_x3s_conv_dgrad": (_I, [_P] * 4 + [_I] * 5 + [_P]),
     "dmc_x3s_conv_wgrad_supported": (_I, [_I] * 5),
     "dmc_x3s_conv_wgrad_bytes": (_Z, [_I] * 5),
@@ -92,6 +93,7 @@ SIGNATURES = {
     "dmc_x3q_merge": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "dmc_x3q_pack_weights": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dmc_x3q_conv_fwd": (_I, [_P] * 6 + [_I] * 6 + [_P]),
+    "dmc_x3q_conv_bn_eval": (_I, [_P] * 11 + [_I] * 5 + [_P]),
     "dmc_x3q_conv_dgrad": (_I, [_P] * 4 + [_I] * 5 + [_P]),
     "dmc_bn_apply_act_x3q": (_I, [_P] * 8 + [_I] * 5 + [_P]),
     "dmc_x3q_conv_wgrad_supported": (_I, [_I] * 5),

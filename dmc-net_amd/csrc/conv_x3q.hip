@@ -97,13 +97,23 @@ struct X3qArgs {
     int pps0, pps1;        // planes per slice of t0 / t1
 };
 
+// EVAL = true (dmc_x3q_conv_bn_eval): the epilogue applies the two BatchNorms with GIVEN statistics (bn_apply_act1, dmc_common.h):
+// main branch relu(bn(acc 0)) -> y0 (fp32, nullable here) and / or ys0 (ordinary slice tensor, nullable), shortcut branch
+// bn(acc 1) -> y1 (fp32, no ReLU).  The training instantiations keep X3qArgs as their kernel argument.
+struct X3qEvalArgs : X3qArgs {
+    const float *stats0, *gamma0, *beta0;      // main branch: mean[R], invstd[R]; gamma; beta
+    const float *stats1, *gamma1, *beta1;      // shortcut branch
+    unsigned short* ys0;                       // [3][R/16][M][16] or null
+};
+
 template <int N, class F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
-template <class P, int TN, class GEO>
-__global__ __launch_bounds__(GEO::NW * 64) void x3q_conv_kernel(X3qArgs a) {
+template <class P, int TN, class GEO, bool EVAL = false>
+__global__ __launch_bounds__(GEO::NW * 64) void x3q_conv_kernel(std::conditional_t<EVAL, X3qEvalArgs, X3qArgs> a) {
+    static_assert(!EVAL || P::NACC == 2, "the eval epilogue belongs to the forward pair");
     constexpr int NSH = P::NSH, NACC = P::NACC, NSTEP = P::NSTEP, NUNIT = P::NUNIT;
     constexpr int QNW = GEO::NW, QNPB = GEO::NPB, QZROW = GEO::ZROW, QPSL = GEO::PSL, QPB = GEO::PB, QWOFF = GEO::WOFF, QPT = GEO::PT;
     constexpr int NA = GEO::NA, KP = GEO::KP, KW = GEO::KW;
@@ -336,6 +346,30 @@ __global__ __launch_bounds__(GEO::NW * 64) void x3q_conv_kernel(X3qArgs a) {
                 *reinterpret_cast<float4*>(etile + l31 * QEP + (32 * j + 8 * g4 + 4 * khalf) * 4) = v;
             }
         float* const yout = (NACC == 2 && A == 1) ? a.y1 : a.y0;
+        if constexpr (EVAL) {
+            // the same row-major read-back; a lane keeps the BatchNorm constants of its four channels, the main branch's slices
+            // leave as 8-byte pieces (x3s_conv_kernel's eval epilogue)
+            const int c4 = rbase + (lane % LPR) * 4;
+            const float* const st = A == 1 ? a.stats1 : a.stats0;
+            const float4 mean = *reinterpret_cast<const float4*>(st + c4), istd = *reinterpret_cast<const float4*>(st + a.R + c4);
+            const float4 gm = *reinterpret_cast<const float4*>((A == 1 ? a.gamma1 : a.gamma0) + c4);
+            const float4 bt = *reinterpret_cast<const float4*>((A == 1 ? a.beta1 : a.beta0) + c4);
+            unsigned short* const ys = A == 1 ? nullptr : a.ys0;
+#pragma unroll
+            for (int it = 0; it < 32 / RPI; ++it) {
+                const int prow = RPI * it + lane / LPR;
+                const int m = mw0 + prow;
+                const float4 v = *reinterpret_cast<const float4*>(etile + prow * QEP + (lane % LPR) * 16);
+                if (m <= mlast) {                                 // pixels beyond M store nothing
+                    const float w[4] = {bn_apply_act1(v.x, mean.x, istd.x, gm.x, bt.x, false, 0.f, A == 0),
+                                        bn_apply_act1(v.y, mean.y, istd.y, gm.y, bt.y, false, 0.f, A == 0),
+                                        bn_apply_act1(v.z, mean.z, istd.z, gm.z, bt.z, false, 0.f, A == 0),
+                                        bn_apply_act1(v.w, mean.w, istd.w, gm.w, bt.w, false, 0.f, A == 0)};
+                    if (yout) *reinterpret_cast<float4*>(yout + (size_t)m * a.R + c4) = make_float4(w[0], w[1], w[2], w[3]);
+                    if (ys) x3s_store4(ys, w, (size_t)a.M, a.R >> 4, (size_t)m, c4 >> 2);
+                }
+            }
+        } else {
 #pragma unroll
         for (int it = 0; it < 32 / RPI; ++it) {
             const int prow = RPI * it + lane / LPR;
@@ -350,7 +384,8 @@ __global__ __launch_bounds__(GEO::NW * 64) void x3q_conv_kernel(X3qArgs a) {
                 *reinterpret_cast<float4*>(yout + opix * a.R + rbase + (lane % LPR) * 4) = v;
             }
         }
-        if (NACC == 2) {
+        }
+        if (NACC == 2 && !EVAL) {                             // (the eval launches write no statistics partials)
             double* const part = A == 1 ? a.part1 : a.part0;
             if (part) {
                 double* red = reinterpret_cast<double*>(lds_q + QNW * QETILE);   // [wm][64 channels][2]
@@ -509,6 +544,17 @@ int launch_q(const X3qArgs& a, hipStream_t s) {
     dim3 grid((a.M + BM - 1) / BM, a.R / QBN);
     x3q_conv_kernel<P, TN, GEO><<<grid, GEO::NW * 64, GEO::LDS, s>>>(a);
     return check_launch("x3q_conv");
+}
+
+template <int TN, class GEO>
+int launch_q_eval(const X3qEvalArgs& a, hipStream_t s) {
+    static LdsLimit lim;
+    const hipError_t attr = lim.raise(reinterpret_cast<const void*>(&x3q_conv_kernel<ProgFwd, TN, GEO, true>), GEO::LDS);
+    if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "x3q_conv_bn_eval: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+    constexpr int BM = 32 * GEO::NW / (2 / TN);
+    dim3 grid((a.M + BM - 1) / BM, a.R / QBN);
+    x3q_conv_kernel<ProgFwd, TN, GEO, true><<<grid, GEO::NW * 64, GEO::LDS, s>>>(a);
+    return check_launch("x3q_conv_bn_eval");
 }
 
 // variant of a launch: 0 = QGBig, TN = 2 (256 pixels); 1 = QGBig, TN = 1 (128 pixels, 32 x 32 wave tiles); 2 = QGTwo (128 pixels,
@@ -917,6 +963,27 @@ int dmc_x3q_conv_fwd(const void* xq, const void* wpack_f, float* y3, float* y1, 
     a.pps0 = 4 * (Cin / 16); a.pps1 = 0;
     return var == 0 ? launch_q<ProgFwd, 2, QGBig>(a, (hipStream_t)stream) : var == 1 ? launch_q<ProgFwd, 1, QGBig>(a, (hipStream_t)stream)
                                                                                       : launch_q<ProgFwd, 2, QGTwo>(a, (hipStream_t)stream);
+}
+
+/* (relu(bn3(conv3x3/s2(x))), bn1(conv1x1/s2(x))) with GIVEN statistics in ONE launch (evaluation; header). */
+int dmc_x3q_conv_bn_eval(const void* xq, const void* wpack_f, const float* stats3, const float* gamma3, const float* beta3,
+                         const float* stats1, const float* gamma1, const float* beta1, float* y3, void* ys3, float* y1, int N, int OH,
+                         int OW, int Cin, int Cout, dmc_stream_t stream) {
+    if (!xq || !wpack_f || !stats3 || !gamma3 || !beta3 || !stats1 || !gamma1 || !beta1 || !y1)
+        return fail(DMC_E_INVALID, "dmc_x3q_conv_bn_eval: null pointer");
+    if (!y3 && !ys3) return fail(DMC_E_INVALID, "dmc_x3q_conv_bn_eval: no main-branch output (y3 and ys3 are both null)");
+    if (!q_shape_ok(N, OH, OW, Cin, Cout))
+        return fail(DMC_E_INVALID, "dmc_x3q_conv_bn_eval: unsupported shape N=%d OH=%d OW=%d Cin=%d Cout=%d", N, OH, OW, Cin, Cout);
+    const int var = q_variant((long)N * OH * OW, OW, Cout);
+    X3qEvalArgs a;
+    a.t0 = xq; a.t1 = nullptr; a.wp = wpack_f; a.y0 = y3; a.y1 = y1; a.part0 = a.part1 = nullptr;
+    a.N = N; a.H = OH; a.W = OW; a.K = Cin; a.R = Cout; a.M = N * OH * OW;
+    a.plane_bytes = (unsigned)a.M * 32u;
+    a.pps0 = 4 * (Cin / 16); a.pps1 = 0;
+    a.stats0 = stats3; a.gamma0 = gamma3; a.beta0 = beta3; a.stats1 = stats1; a.gamma1 = gamma1; a.beta1 = beta1;
+    a.ys0 = static_cast<unsigned short*>(ys3);
+    return var == 0 ? launch_q_eval<2, QGBig>(a, (hipStream_t)stream) : var == 1 ? launch_q_eval<1, QGBig>(a, (hipStream_t)stream)
+                                                                                  : launch_q_eval<2, QGTwo>(a, (hipStream_t)stream);
 }
 
 int dmc_x3q_conv_dgrad(const void* dys3, const void* dys1, const void* wpack_t, float* dx, int N, int OH, int OW, int Cin, int Cout,

@@ -121,6 +121,17 @@ struct X3Args {
     int ablate;            // measurement only (option conv_ablate): 16 = no wait for transfers, 32 = no statistics, 64 = no transfers,
                            // 128 = no output stores, 256 = no main loop (results wrong / missing)
 };
+// EVAL = true (dmc_x3s_conv_bn_eval): the epilogue applies the BatchNorm with GIVEN statistics [+ shortcut] [+ ReLU] to the tile
+// (bn_apply_act1, dmc_common.h) and writes the result as fp32 (y, nullable here) and / or as a slice tensor -- the
+// convolution's own fp32 result never reaches memory.  The training instantiations keep X3Args as their kernel argument.
+struct X3EvalArgs : X3Args {
+    const float* stats;    // mean[R], invstd[R]
+    const float* gamma;
+    const float* beta;
+    const float* res;      // shortcut [M][R] fp32 or null: added behind the BatchNorm
+    unsigned short* ys;    // slice tensor of the result or null: [3][R/16][M][16], or space-to-depth over the [N][H][W] grid
+    int s2d, relu;
+};
 
 // WM waves along pixels x WN along channels; a wave owns TM x TN tiles of 32 pixels x 32 channels.
 // BN = 32 TN WN must be 64 (the packed weight image); PPMAX = patch pixels the LDS is laid out for.
@@ -132,8 +143,9 @@ struct X3Args {
 // with ty = 1 (py = 0) or ty in {0, 2} (py = 1), likewise in x: 1 + 2 + 2 + 4 = 9 (tap, class) pairs, every tap feeds
 // exactly one class's accumulators, reading dy at offset (+1 for t = 0, else 0) -- the same step structure, four accumulator
 // sets, no multiply on structural zeros (the in-loop-split path issued four small launches per convolution).
-template <int WM, int WN, int TM, int TN, int PPMAX, bool STAG = false, int CLS = 1>
-__global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(X3Args a) {
+template <int WM, int WN, int TM, int TN, int PPMAX, bool STAG = false, int CLS = 1, bool EVAL = false>
+__global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(std::conditional_t<EVAL, X3EvalArgs, X3Args> a) {
+    static_assert(!EVAL || CLS == 1, "the eval epilogue belongs to the forward convolution");
     constexpr int NW = WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
     static_assert(BN == 64, "packed weight image is 64 rows wide");
     // patch transfers move 32 pixel rows: the staged pixels (<= PPMAX - 1) end on a transfer boundary or the zero row is the
@@ -386,6 +398,42 @@ __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(X3Args a) {
                     *reinterpret_cast<float4*>(etile + (32 * i + l31) * EP + (32 * j + 8 * g + 4 * khalf) * 4) = v;
                 }
         }
+        if constexpr (EVAL) {
+            // the same row-major read-back (16 lanes = one 256-byte pixel row, four rows per instruction: conflict-free under the
+            // ds_read_b128 lane groups at the 272-byte pitch); a lane keeps the BatchNorm constants of its four channels in
+            // registers, the slices leave as 8-byte pieces -- four consecutive pixels of a chunk plane are one 128-byte line
+            const int c4 = rbase + (lane & 15) * 4;
+            const float4 mean = *reinterpret_cast<const float4*>(a.stats + c4), istd = *reinterpret_cast<const float4*>(a.stats + a.R + c4);
+            const float4 gm = *reinterpret_cast<const float4*>(a.gamma + c4), bt = *reinterpret_cast<const float4*>(a.beta + c4);
+            const bool has_res = a.res != nullptr, relu = a.relu != 0;
+            const int ochunk = a.R >> 4;
+#pragma unroll
+            for (int it = 0; it < 8 * TM; ++it) {
+                const int prow = 4 * it + (lane >> 4);
+                const int m = mw0 + prow;
+                const float4 v = *reinterpret_cast<const float4*>(etile + prow * EP + (lane & 15) * 16);
+                if (m <= mlast) {                                 // pixels beyond M store nothing
+                    const size_t o = (size_t)m * a.R + c4;
+                    float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (has_res) rv = *reinterpret_cast<const float4*>(a.res + o);
+                    const float w[4] = {bn_apply_act1(v.x, mean.x, istd.x, gm.x, bt.x, has_res, rv.x, relu),
+                                        bn_apply_act1(v.y, mean.y, istd.y, gm.y, bt.y, has_res, rv.y, relu),
+                                        bn_apply_act1(v.z, mean.z, istd.z, gm.z, bt.z, has_res, rv.z, relu),
+                                        bn_apply_act1(v.w, mean.w, istd.w, gm.w, bt.w, has_res, rv.w, relu)};
+                    if (a.y) *reinterpret_cast<float4*>(a.y + o) = make_float4(w[0], w[1], w[2], w[3]);
+                    if (a.ys) {
+                        if (a.s2d) {      // pixel (n, y, x) -> parity class 2 (y & 1) + (x & 1), position (n, y / 2, x / 2) (bn_act.hip)
+                            const int n = m / HW, rem = m - n * HW, yy = rem / a.W, xx = rem - yy * a.W;
+                            const int cls = (yy & 1) * 2 + (xx & 1);
+                            const size_t mq = ((size_t)n * (a.H >> 1) + (yy >> 1)) * (a.W >> 1) + (xx >> 1);
+                            x3s_store4(a.ys, w, (size_t)a.M >> 2, 4 * ochunk, mq, (c4 >> 2) + cls * 4 * ochunk);
+                        } else {
+                            x3s_store4(a.ys, w, (size_t)a.M, ochunk, (size_t)m, c4 >> 2);
+                        }
+                    }
+                }
+            }
+        } else
         if (!(DMC_ABL(a.ablate) & 128)) {
 #pragma unroll
             for (int it = 0; it < 8 * TM; ++it) {
@@ -433,6 +481,7 @@ __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(X3Args a) {
             }
         }
     }
+    if constexpr (EVAL) return;                              // the eval launches write no statistics partials
     if (CLS == 1 && a.bnb_part) {
         // lane = channel: column sums of d and d * xhat over the wave's pixels, fp64, fixed order
         double* red = reinterpret_cast<double*>(lds_x3 + NW * ETILE);   // [WM][64][2]
@@ -586,6 +635,24 @@ int run_x3s(const void* xs, const void* wp, const float* addend, float* y, doubl
         case 4: return launch_x3s<4, 1, 225>(a, s);
         default: return fail(DMC_E_INVALID, "x3s_conv: the patch of a %d x %d image does not fit the LDS", H, W);
     }
+}
+
+// ---- forward with the eval-mode BatchNorm epilogue (dmc_x3s_conv_bn_eval) -----------------------------------------
+// The tile configurations of the training forward (x3s_choose, option conv_cfg), staggered transfers wherever there are four
+// waves; the epilogue needs the waves' fp32 tiles only (no sums, no xhat tiles), which the operand LDS always covers.
+// Of the options only conv_cfg is obeyed (through x3s_choose): the measurement option conv_ablate -- bit 512 of which makes the
+// training launch take the non-staggered kernel -- is not read here, and the kernel's ablation switches get 0.
+template <int WM, int TM, int PPMAX>
+int launch_x3s_eval(const X3EvalArgs& a, hipStream_t s) {
+    constexpr int BM = 32 * TM * WM;
+    constexpr size_t lds_bytes = 2 * 3 * PPMAX * 32 + 2 * 3 * 3 * 64 * 32;
+    static_assert((size_t)BM * 272 <= lds_bytes, "the epilogue tiles live in the operand LDS");
+    dim3 grid((a.M + BM - 1) / BM, a.R / 64);
+    static LdsLimit lim_attr;
+    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX, (WM >= 4), 1, true>), (int)lds_bytes);
+    if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "x3s_conv_bn_eval: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+    x3s_conv_kernel<WM, 1, TM, 2, PPMAX, (WM >= 4), 1, true><<<grid, WM * 64, lds_bytes, s>>>(a);
+    return check_launch("x3s_conv_bn_eval");
 }
 
 // ---- weight gradient ------------------------------------------------------------------------------------
@@ -895,6 +962,34 @@ int dmc_x3s_conv_stat_blocks(int N, int H, int W, int Cout) {
 int dmc_x3s_conv_fwd(const void* xs, const void* wpack_f, float* y, double* stat_partials, int stat_blocks, int N, int H, int W,
                      int Cin, int Cout, dmc_stream_t stream) {
     return run_x3s(xs, wpack_f, nullptr, y, stat_partials, stat_blocks, N, H, W, Cin, Cout, (hipStream_t)stream);
+}
+
+/* relu?(bn(conv3x3(x)) [+ residual]) with GIVEN statistics in ONE launch (evaluation; header). */
+int dmc_x3s_conv_bn_eval(const void* xs, const void* wpack_f, const float* stats, const float* gamma, const float* beta,
+                         const float* residual, float* y, void* ys, int s2d, int relu, int N, int H, int W, int Cin, int Cout,
+                         dmc_stream_t stream) {
+    if (!xs || !wpack_f || !stats || !gamma || !beta) return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: null pointer");
+    if (!y && !ys) return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: no output (y and ys are both null)");
+    if (s2d && !ys) return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: s2d describes the slice output, which is null");
+    if (s2d && ((H & 1) || (W & 1))) return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: a space-to-depth result needs even H and W (H=%d W=%d)", H, W);
+    if (Cin % 64 != 0 || Cout % 64 != 0 || !x3s_shape_ok(N, H, W, Cin, Cout) || !x3s_shape_ok(N, H, W, Cout, Cin))
+        return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: unsupported shape N=%d H=%d W=%d Cin=%d Cout=%d", N, H, W, Cin, Cout);
+    X3EvalArgs a;
+    a.xs = xs; a.wp = wpack_f; a.y = y; a.addend = nullptr; a.stat_part = nullptr;
+    a.N = N; a.H = H; a.W = W; a.K = Cin; a.R = Cout; a.M = N * H * W;
+    a.plane_bytes = (unsigned)a.M * 32u;
+    a.ablate = 0;
+    a.stats = stats; a.gamma = gamma; a.beta = beta; a.res = residual; a.ys = static_cast<unsigned short*>(ys);
+    a.s2d = s2d ? 1 : 0; a.relu = relu ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    switch (x3s_choose(N, H, W, Cout)) {
+        case 0: return launch_x3s_eval<8, 1, 608>(a, s);
+        case 1: return launch_x3s_eval<4, 1, 320>(a, s);
+        case 2: return launch_x3s_eval<2, 1, 192>(a, s);
+        case 3: return launch_x3s_eval<4, 2, 608>(a, s);
+        case 4: return launch_x3s_eval<4, 1, 225>(a, s);
+        default: return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: the patch of a %d x %d image does not fit the LDS", H, W);
+    }
 }
 
 int dmc_x3s_conv_dgrad(const void* dys, const void* wpack_t, const float* addend, float* dx, int N, int H, int W, int Cin, int Cout,

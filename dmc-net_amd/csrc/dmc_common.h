@@ -238,4 +238,34 @@ __device__ __forceinline__ void x3s_store8(unsigned short* __restrict__ xs, cons
     *reinterpret_cast<x3s_u32x4*>(xs + (size_t)nchunk * plane + w) = s1;
     *reinterpret_cast<x3s_u32x4*>(xs + (size_t)2 * nchunk * plane + w) = s2;
 }
+// the three slices of 4 consecutive channels (4 q .. 4 q + 3) of pixel m -> xs: the same split and packing as x3s_store8, in
+// 8-byte pieces (the eval epilogues of conv_x3s.hip / conv_x3q.hip, whose lanes hold four channels of a pixel)
+typedef unsigned x3s_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void x3s_store4(unsigned short* __restrict__ xs, const float (&v)[4], size_t M, int nchunk, size_t m, int q) {
+    unsigned u0[4], u1[4], u2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x3s_split3(v[e], u0[e], u1[e], u2[e]);
+    x3s_u32x2 s0, s1, s2;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        s0[e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
+        s1[e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
+        s2[e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
+    }
+    const size_t plane = M * 16;
+    const size_t w = ((size_t)(q >> 2) * M + m) * 16 + (size_t)(q & 3) * 4;
+    *reinterpret_cast<x3s_u32x2*>(xs + w) = s0;
+    *reinterpret_cast<x3s_u32x2*>(xs + (size_t)nchunk * plane + w) = s1;
+    *reinterpret_cast<x3s_u32x2*>(xs + (size_t)2 * nchunk * plane + w) = s2;
+}
+
+// ---- BatchNorm with GIVEN statistics [+ shortcut] [+ ReLU] on one value: the expression and the order of bn_apply_fwd_kernel /
+// bn_apply_fwd_x3s_kernel (bn_act.hip).  The build has -ffp-contract=off, so a convolution epilogue that applies it to its
+// accumulator gives the bits of the convolution followed by that streaming pass.
+__device__ __forceinline__ float bn_apply_act1(float x, float mean, float istd, float gamma, float beta, bool has_res, float res, bool relu) {
+    float v = fmaf((x - mean) * istd, gamma, beta);
+    if (has_res) v += res;
+    if (relu) v = fmaxf(v, 0.f);
+    return v;
+}
 }  // namespace dmc

@@ -1333,40 +1333,70 @@ def conv_bn_eval_supported(x, conv, bn):
     return bool(_lib.load().dmc_bn_act_supported(n * oh * ow, conv.out_channels)) and conv.out_channels % 16 == 0
 
 
-def conv_bn_act_eval(x, conv, bn, residual=None, relu=True, want_f32=True, want_slices=False):
-    """Forward-only relu?(bn(conv(x)) [+ residual]) with the BatchNorm's RUNNING statistics (eval mode, no autograd): the
-    same convolution kernels as the training op (pre-split path for stride-1 3x3), no statistics epilogue, and the
-    normalisation as one streaming pass with (mean, 1 / sqrt(var + eps)) taken from the module's buffers."""
+def _bn_eval_stats(bn):
+    """[mean[C], 1 / sqrt(var + eps)[C]] of a BatchNorm's running statistics.  Built on EVERY call: the training kernels update the
+    buffers through raw pointers, which a tensor version counter does not see, so nothing derived from them may be cached."""
+    return torch.cat([bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)]).contiguous()
+
+
+def conv_bn_act_eval(x, conv, bn, residual=None, relu=True, want_f32=True, want_slices=False, s2d=False, fused=True):
+    """Forward-only relu?(bn(conv(x)) [+ residual]) with the BatchNorm's RUNNING statistics (eval mode, no autograd).
+
+    A convolution on the pre-split path (x3s_usable) is ONE launch, dmc_x3s_conv_bn_eval: the normalisation, the shortcut and
+    the ReLU run in the convolution's epilogue and no fp32 convolution result reaches memory.  ``fused=False`` -- and every
+    other convolution -- takes two passes: the convolution kernel of the training op without its statistics epilogue, then
+    the normalisation as one streaming pass; the results are bit-identical.  ``want_slices``: the result's slice tensor is
+    written too (x3s_of); ``s2d``: that tensor is space-to-depth (x3q_of) for a stride-2 pair that is the result's only
+    reader; ``want_f32=False``: slices only, the returned tensor's fp32 memory stays unwritten (f32_valid)."""
     lib = _lib.load()
     _need_cuda(x, conv.weight, residual)
     n, cin, h, w = x.shape
     cout = conv.out_channels
     wcl = _as_cl(conv.weight.detach())
     stride, padding = conv.stride[0], conv.padding[0]
-    if x3s_usable(n, h, w, conv):
-        xs = x3s_of(x)
-        if xs is None:
-            xs = x3s_split(_as_cl(x))
-        wf, _ = x3s_pack_weights(wcl, forward=True, transposed=False)
-        y, _ = x3s_conv_fwd(xs, wf, n, h, w, cin, cout)
-    else:
-        if not f32_valid(x):
-            raise RuntimeError("conv_bn_act_eval: the input's fp32 memory was not written by its producer (slices only)")
-        y, _, _ = _conv_fwd(_as_cl(x), wcl, None, None, stride, padding, 0, False)
-    m = y.shape[0] * y.shape[2] * y.shape[3]
-    stats = torch.cat([bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)]).contiguous()
     if not want_f32 and not want_slices:
         want_f32 = True
-    out = torch.empty_like(y)
-    out_xs = _x3s_buffer(m, cout, x.device) if want_slices else None
+    s2d = bool(s2d and want_slices)
     if residual is not None:
         if not f32_valid(residual):
             raise RuntimeError("conv_bn_act_eval: the residual's fp32 memory was not written by its producer")
         residual = _as_cl(residual)
-    _lib.check(lib.dmc_bn_apply_act_x3s(_lib.ptr(y), _lib.ptr(residual), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(stats),
-                                        _lib.ptr(out) if want_f32 else None, _lib.ptr(out_xs), None, m, cout, int(relu),
-                                        _stream()), "dmc_bn_apply_act_x3s")
-    if want_slices:
+    use_x3s = x3s_usable(n, h, w, conv)
+    if use_x3s:
+        xs = x3s_of(x)
+        if xs is None:
+            if not f32_valid(x):
+                raise RuntimeError("conv_bn_act_eval: the input carries neither slices nor valid fp32 memory")
+            xs = x3s_split(_as_cl(x))
+        wf, _ = x3s_pack_weights(wcl, forward=True, transposed=False)
+    stats = _bn_eval_stats(bn)
+    if use_x3s and fused:
+        out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device, memory_format=_CL)
+        out_xs = _x3s_buffer(n * h * w, cout, x.device) if want_slices else None
+        _lib.check(lib.dmc_x3s_conv_bn_eval(_lib.ptr(xs), _lib.ptr(wf), _lib.ptr(stats), _lib.ptr(bn.weight), _lib.ptr(bn.bias),
+                                            _lib.ptr(residual), _lib.ptr(out) if want_f32 else None, _lib.ptr(out_xs), int(s2d),
+                                            int(relu), n, h, w, cin, cout, _stream()), "dmc_x3s_conv_bn_eval")
+    else:
+        if use_x3s:
+            y, _ = x3s_conv_fwd(xs, wf, n, h, w, cin, cout)
+        else:
+            if not f32_valid(x):
+                raise RuntimeError("conv_bn_act_eval: the input's fp32 memory was not written by its producer (slices only)")
+            y, _, _ = _conv_fwd(_as_cl(x), wcl, None, None, stride, padding, 0, False)
+        m = y.shape[0] * y.shape[2] * y.shape[3]
+        out = torch.empty_like(y)
+        out_xs = _x3s_buffer(m, cout, x.device) if want_slices else None
+        if s2d:
+            _lib.check(lib.dmc_bn_apply_act_x3q(_lib.ptr(y), _lib.ptr(residual), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(stats),
+                                                _lib.ptr(out) if want_f32 else None, _lib.ptr(out_xs), None, y.shape[0], y.shape[2],
+                                                y.shape[3], cout, int(relu), _stream()), "dmc_bn_apply_act_x3q")
+        else:
+            _lib.check(lib.dmc_bn_apply_act_x3s(_lib.ptr(y), _lib.ptr(residual), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(stats),
+                                                _lib.ptr(out) if want_f32 else None, _lib.ptr(out_xs), None, m, cout, int(relu),
+                                                _stream()), "dmc_bn_apply_act_x3s")
+    if s2d:
+        out._dmc_x3q, out._dmc_f32 = out_xs, want_f32
+    elif want_slices:
         _attach_x3s(out, out_xs, want_f32)
     return out
 
@@ -1556,6 +1586,78 @@ def conv_bn_s2_pair(x, unit, want_slices):
     out3, out3_xs, out1 = _ConvBnS2Pair.apply(x, xq, unit.conv1.weight, unit.downsample[0].weight, bn3.weight, bn3.bias,
                                               bn3.running_mean, bn3.running_var, bn3.eps, bn3.momentum, bn1.weight, bn1.bias,
                                               bn1.running_mean, bn1.running_var, bn1.eps, bn1.momentum, bool(want_slices))
+    if want_slices:
+        _attach_x3s(out3, out3_xs, False)
+    return out3, out1
+
+
+def _bn_evals(bn):
+    return (not bn.training) and bn.track_running_stats and bn.affine
+
+
+def _s2_pair_eval_unit_ok(unit):
+    """The part of s2_pair_eval_usable that looks at modes and structure only (no device, no shape): autograd off, a "basic" unit
+    whose conv1 is 3x3 / stride 2 / padding 1 and whose downsample is (1x1 / stride 2, BatchNorm2d), both bias-free fp32, both
+    BatchNorms in eval mode with running statistics."""
+    if not (X3Q and X3S) or torch.is_grad_enabled():
+        return False
+    ds = getattr(unit, "downsample", None)
+    if getattr(unit, "kind", None) != "basic" or ds is None or len(ds) != 2:
+        return False
+    for c, k, p in ((unit.conv1, (3, 3), (1, 1)), (ds[0], (1, 1), (0, 0))):
+        if not isinstance(c, torch.nn.Conv2d) or c.kernel_size != k or c.stride != (2, 2) or c.padding != p or c.bias is not None:
+            return False
+        if c.dilation != (1, 1) or c.groups != 1 or c.padding_mode != "zeros" or c.weight.dtype != torch.float32:
+            return False
+    return isinstance(ds[1], torch.nn.BatchNorm2d) and _bn_evals(unit.bn1) and _bn_evals(ds[1])
+
+
+def s2_pair_eval_usable(x_shape, unit):
+    """The no-grad, eval-BatchNorm counterpart of s2_pair_usable: True if ``unit`` (a "basic" resnet.ResidualUnit with a
+    downsample branch, on the GPU) on an input of ``x_shape`` takes conv_bn_s2_pair_eval -- conv1 3x3 / stride 2 / padding 1 and
+    downsample = (1x1 / stride 2, BatchNorm2d), both bias-free, both BatchNorms in eval mode with running statistics, autograd
+    off, a shape the forward kernel covers (no weight gradient is needed).  The producer of the block input asks the same
+    question before it writes space-to-depth slices and leaves the fp32 form unwritten."""
+    if not _s2_pair_eval_unit_ok(unit):
+        return False
+    c3, c1 = unit.conv1, unit.downsample[0]
+    if not (c3.weight.is_cuda and c1.weight.is_cuda):
+        return False
+    n, cin, h, w = x_shape
+    cout = c3.out_channels
+    if c3.in_channels != cin or c1.in_channels != cin or c1.out_channels != cout or (h & 1) or (w & 1):
+        return False
+    lib = _lib.load()
+    if lib.dmc_get_option(b"conv_arith") != 1 or lib.dmc_get_option(b"conv_path") != 1:
+        return False
+    return bool(lib.dmc_x3q_supported(n, h // 2, w // 2, cin, cout))
+
+
+def conv_bn_s2_pair_eval(x, unit, want_slices):
+    """(relu(bn1(conv1(x))), downsample(x)) of a stride-2 BasicBlock ``unit`` in eval mode (see s2_pair_eval_usable): ONE launch,
+    dmc_x3q_conv_bn_eval, for both convolutions and both running-statistics BatchNorms.  ``x`` carries its space-to-depth
+    slice tensor (x3q_of) or valid fp32 memory, which is split on the fly; ``want_slices``: conv2 of the unit takes the
+    pre-split path, the first result is returned as slices only (x3s_of)."""
+    lib = _lib.load()
+    bn3, bn1 = unit.bn1, unit.downsample[1]
+    w3, w1 = unit.conv1.weight.detach(), unit.downsample[0].weight.detach()
+    _need_cuda(x, w3, w1)
+    xq = x3q_of(x)
+    if xq is None:
+        if not f32_valid(x):
+            raise RuntimeError("conv_bn_s2_pair_eval: the input carries neither s2d slices nor valid fp32 memory")
+        xq = x3q_split(_as_cl(x))
+    n, cin, h, w = x.shape
+    cout, oh, ow = w3.shape[0], h // 2, w // 2
+    wf, _ = x3q_pack_weights(w3, w1, forward=True, transposed=False)
+    stats3, stats1 = _bn_eval_stats(bn3), _bn_eval_stats(bn1)
+    out3 = torch.empty((n, cout, oh, ow), dtype=torch.float32, device=x.device, memory_format=_CL)   # not written when conv2 reads slices only
+    out3_xs = _x3s_buffer(n * oh * ow, cout, x.device) if want_slices else None
+    out1 = torch.empty_like(out3)
+    _lib.check(lib.dmc_x3q_conv_bn_eval(_lib.ptr(xq), _lib.ptr(wf), _lib.ptr(stats3), _lib.ptr(bn3.weight), _lib.ptr(bn3.bias),
+                                        _lib.ptr(stats1), _lib.ptr(bn1.weight), _lib.ptr(bn1.bias),
+                                        None if want_slices else _lib.ptr(out3), _lib.ptr(out3_xs), _lib.ptr(out1), n, oh, ow, cin, cout,
+                                        _stream()), "dmc_x3q_conv_bn_eval")
     if want_slices:
         _attach_x3s(out3, out3_xs, False)
     return out3, out1

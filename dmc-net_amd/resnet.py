@@ -37,6 +37,11 @@ OWN_CONV = _os.environ.get("DMC_OWN_CONV", "1") != "0"
 KEEP_F32_OUTPUTS = _os.environ.get("DMC_KEEP_F32_OUTPUTS", "0") == "1"
 # identity-shortcut blocks: residual gradient added in the first convolution's data-gradient epilogue (ops.ResidualGradLink)
 RESIDUAL_GRAD_LINK = _os.environ.get("DMC_RESIDUAL_GRAD_LINK", "1") != "0"
+#: True (default): under model.eval() + no_grad every pre-split 3x3 unit is ONE launch (ops.conv_bn_act_eval: the BatchNorm, the
+#: shortcut and the ReLU in the convolution's epilogue) and conv1 + downsample of a stride-2 block are ONE launch of the pair kernel
+#: (ops.conv_bn_s2_pair_eval).  DMC_EVAL_FUSED=0: the two-pass route (convolution, then a streaming BatchNorm pass; the stride-2
+#: blocks on two launches of the in-loop-split kernel) -- the A/B comparator, 5-6 % slower on the evaluator's batch.
+EVAL_FUSED = _os.environ.get("DMC_EVAL_FUSED", "1") != "0"
 
 
 def _same_bn_mode(bn, other):
@@ -45,6 +50,13 @@ def _same_bn_mode(bn, other):
     momentum=None, affine=False ...) keeps the fp32 form and the consumer falls back to the stock modules."""
     return (other is not None and other.training == bn.training and other.track_running_stats and other.affine
             and other.momentum is not None)
+
+
+def _out_shape(conv, x):
+    """Shape of conv(x) for a square kernel / stride / padding."""
+    n, _, h, w = x.shape
+    k, s_, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+    return (n, conv.out_channels, (h + 2 * p - k) // s_ + 1, (w + 2 * p - k) // s_ + 1)
 
 
 def _conv_bn_act(conv, bn, x, residual=None, relu=True, link=None, next_conv=None, only_consumer=False, bn_link=None,
@@ -58,20 +70,21 @@ def _conv_bn_act(conv, bn, x, residual=None, relu=True, link=None, next_conv=Non
     if train_op and next_unit is not None:
         # the result is the input of a stride-2 block: its conv1 and its shortcut convolution both read the space-to-depth
         # slice tensor (ops.conv_bn_s2_pair) and nothing reads the fp32 form
-        n, _, h, w = x.shape
-        k, s_, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        oshape = (n, conv.out_channels, (h + 2 * p - k) // s_ + 1, (w + 2 * p - k) // s_ + 1)
-        if ops.s2_pair_usable(oshape, next_unit):
+        if ops.s2_pair_usable(_out_shape(conv, x), next_unit):
             return ops.conv_bn_act(x, conv, bn, residual, relu, link, want_f32=False, want_slices=True, s2d=True)
+    if eval_op and EVAL_FUSED and next_unit is not None:
+        # evaluation, same rule: the stride-2 block that follows reads space-to-depth slices (ops.conv_bn_s2_pair_eval)
+        if ops.s2_pair_eval_usable(_out_shape(conv, x), next_unit):
+            return ops.conv_bn_act_eval(x, conv, bn, residual, relu, want_f32=False, want_slices=True, s2d=True)
     if train_op or eval_op:
         slices = False
         if next_conv is not None:
-            n, _, h, w = x.shape
-            k, s_, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-            slices = ops.x3s_usable(n, (h + 2 * p - k) // s_ + 1, (w + 2 * p - k) // s_ + 1, next_conv)
+            n, _, oh, ow = _out_shape(conv, x)
+            slices = ops.x3s_usable(n, oh, ow, next_conv)
             only_consumer = only_consumer and _same_bn_mode(bn, next_bn)
         if eval_op:     # evaluation / validation: running statistics, forward only, the same convolution kernels
-            return ops.conv_bn_act_eval(x, conv, bn, residual, relu, want_f32=not (slices and only_consumer), want_slices=slices)
+            return ops.conv_bn_act_eval(x, conv, bn, residual, relu, want_f32=not (slices and only_consumer), want_slices=slices,
+                                        fused=EVAL_FUSED)
         return ops.conv_bn_act(x, conv, bn, residual, relu, link, want_f32=not (slices and only_consumer), want_slices=slices,
                                bn_link=bn_link if slices else None)
     if not ops.f32_valid(x):
@@ -135,6 +148,13 @@ class ResidualUnit(nn.Module):
             return _conv_bn_act(self.conv2, self.bn2, y, residual=shortcut, next_conv=self.next_conv[0],
                                 bn_link="block" if (self.next_identity[0] and RESIDUAL_GRAD_LINK) else None,
                                 next_unit=self._next_unit())
+        elif (OWN_CONV and EVAL_FUSED and x.is_cuda and ops.s2_pair_eval_usable(tuple(x.shape), self)
+              and (ops.x3q_of(x) is not None or ops.f32_valid(x))):
+            # the same pair in evaluation: one launch, both running-statistics BatchNorms in its epilogue
+            n, _, h, w = x.shape
+            y, shortcut = ops.conv_bn_s2_pair_eval(x, self, want_slices=ops.x3s_usable(n, h // 2, w // 2, self.conv2) and
+                                                   _same_bn_mode(self.bn1, self.bn2))
+            return _conv_bn_act(self.conv2, self.bn2, y, residual=shortcut, next_conv=self.next_conv[0], next_unit=self._next_unit())
         else:
             shortcut = _conv_bn_act(self.downsample[0], self.downsample[1], x, relu=False)
         # conv1's result is read by conv2 alone: slices only when conv2 takes the pre-split path

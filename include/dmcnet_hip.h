@@ -424,6 +424,19 @@ int dmc_x3s_conv_fwd(const void* xs, const void* wpack_f, float* y, double* stat
                      int Cin, int Cout, dmc_stream_t stream);
 int dmc_x3s_conv_dgrad(const void* dys, const void* wpack_t, const float* addend, float* dx, int N, int H, int W, int Cin,
                        int Cout, dmc_stream_t stream);
+/* The forward convolution with the eval-mode BatchNorm [+ shortcut] [+ ReLU] in its epilogue, ONE launch:
+ * Replaces: the stride-1 3x3 convolution + BatchNorm2d (running statistics) [+ `out += identity`] [+ ReLU] of torchvision's
+ *           BasicBlock (behind code/dmcnet/model.py:305,352) as the evaluator runs them under model.eval() + no_grad
+ *           (code/dmcnet/test.py:139-198, validate() of code/dmcnet/train.py) -- what dmc_x3s_conv_fwd followed by
+ *           dmc_bn_apply_act_x3s / dmc_bn_apply_act_x3q computes, bit for bit, without the fp32 convolution result in memory.
+ * stats = mean[Cout], 1 / sqrt(var + eps)[Cout] (as dmc_bn_apply_act_x3s takes them); residual: fp32 [M][Cout] or NULL.
+ * Outputs (at least one): y fp32 [M][Cout] (nullable); ys (nullable) the result's slice tensor, [3][Cout/16][M][16] when
+ * s2d == 0, the space-to-depth tensor of dmc_bn_apply_act_x3q over the [N][H][W] grid (H, W even) when s2d != 0.
+ * Shapes of dmc_x3s_conv_supported(); obeys option conv_cfg as dmc_x3s_conv_fwd does; writes no statistics partials.
+ * DMC_E_INVALID before any launch: a null input, no output, s2d without ys or with odd H / W, Cin or Cout % 64 != 0. */
+int dmc_x3s_conv_bn_eval(const void* xs, const void* wpack_f, const float* stats, const float* gamma, const float* beta,
+                         const float* residual, float* y, void* ys, int s2d, int relu, int N, int H, int W, int Cin, int Cout,
+                         dmc_stream_t stream);
 /* wgrad: dw [Cout][3][3][Cin] fp32 (channels_last memory of the PyTorch gradient) from the slice tensors of x and dy;
  * workspace of dmc_x3s_conv_wgrad_bytes() (per-workgroup-row partials, summed in fixed order).  W in {56, 28, 14, 7}. */
 int dmc_x3s_conv_wgrad_supported(int N, int H, int W, int Cin, int Cout);
@@ -495,6 +508,19 @@ int dmc_x3q_conv_fwd(const void* xq, const void* wpack_f, float* y3, float* y1, 
                      int stat_blocks, int N, int OH, int OW, int Cin, int Cout, dmc_stream_t stream);
 int dmc_x3q_conv_dgrad(const void* dys3, const void* dys1, const void* wpack_t, float* dx, int N, int OH, int OW, int Cin, int Cout,
                        dmc_stream_t stream);
+/* The forward pair with both eval-mode BatchNorms in its epilogue, ONE launch:
+ * Replaces: `conv1` + `bn1` + ReLU and `downsample` (1x1 convolution + BatchNorm2d) of torchvision's stride-2 BasicBlock
+ *           (layer2.0 / layer3.0 / layer4.0 behind code/dmcnet/model.py:305,352) with running statistics, as the evaluator
+ *           runs them (code/dmcnet/test.py:139-198, validate() of code/dmcnet/train.py) -- what dmc_x3q_conv_fwd followed by
+ *           dmc_bn_apply_act_x3s (main branch) and dmc_bn_apply_act_nhwc (shortcut branch) computes, bit for bit.
+ * stats3 / stats1 = mean[Cout], 1 / sqrt(var + eps)[Cout] of bn1 / the downsample BatchNorm.
+ * Main branch relu(bn3(conv3x3/s2)): y3 fp32 [Mq][Cout] (nullable) and / or ys3 its ordinary slice tensor
+ * [3][Cout/16][Mq][16] (nullable), at least one; shortcut branch bn1(conv1x1/s2): y1 fp32 [Mq][Cout], no ReLU.
+ * Shapes of dmc_x3q_supported(); obeys option conv_cfg as dmc_x3q_conv_fwd does; writes no statistics partials.
+ * DMC_E_INVALID before any launch: a null input or y1, neither y3 nor ys3, Cin or Cout % 64 != 0. */
+int dmc_x3q_conv_bn_eval(const void* xq, const void* wpack_f, const float* stats3, const float* gamma3, const float* beta3,
+                         const float* stats1, const float* gamma1, const float* beta1, float* y3, void* ys3, float* y1, int N, int OH,
+                         int OW, int Cin, int Cout, dmc_stream_t stream);
 /* dmc_bn_apply_act_x3s (BatchNorm apply [+ residual] [+ ReLU] with given statistics) whose slice output yq is the s2d
  * tensor over the [N][H][W] grid; y (fp32 NHWC, nullable) as usual. */
 int dmc_bn_apply_act_x3q(const float* x, const float* residual, const float* gamma, const float* beta, const float* stats,
