@@ -29,10 +29,14 @@ SIGNATURES = {
     "dmc_gen_tiny_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dmc_gen_tiny_mse_partials_bytes": (_Z, []),
     "dmc_gen_tiny_fwd_mse": (_I, [_P] * 10 + [_I, _I, _I, _I, _P]),
+    "dmc_gen_tiny_fwd_loss": (_I, [_I] + [_P] * 10 + [_I, _I, _I, _I, _P]),
     "dmc_gen_tiny_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dmc_flow_mse_partials_bytes": (_Z, []),
     "dmc_flow_mse_fwd": (_I, [_P, _P, _P, _P, _Z, _P]),
     "dmc_flow_mse_bwd": (_I, [_P, _P, _P, _P, _Z, _P]),
+    "dmc_flow_loss_partials_bytes": (_Z, []),
+    "dmc_flow_loss_fwd": (_I, [_I, _P, _P, _P, _P, _P, _Z, _P]),
+    "dmc_flow_loss_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "dmc_consensus_ce_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dmc_disc_tail_stats_bytes": (_Z, [_I]),
     "dmc_disc_tail_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),

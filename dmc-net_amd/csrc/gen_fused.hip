@@ -66,7 +66,7 @@ struct FusedArgs {
     float* out;           // [N,2,H,W]
     ParamPtrs prm;        // the twelve parameter tensors as PyTorch holds them (w[k]: [Cout][Cin_logical][3][3]): read once per wave
     const float* flow;    // [N,2,H,W] or null
-    double* mse_part;     // [gridDim.x * 2]
+    double* mse_part;     // [gridDim.x * 2]: per-wave sums of the loss terms l(out - flow) (the kind is a template argument of the kernel)
     int H, W, add_mv;
     int nstrips, sw, m;   // strips per frame; strip width in LDS columns; first image column the second strip owns
     int vsplit, vhalo;    // row bands per strip; rows a band recomputes above / below
@@ -115,6 +115,19 @@ __device__ __forceinline__ int fz_steps(int H) { return (H + FZ_LAG + 1 + 2) / 3
 // shifted by 3 Cout rows with register moves after each step.  A set starts its life with the first MFMA of a step taking
 // a ZERO C operand (whole fresh tiles; the rows of a shared tile are zeroed by the shift), the bias joins in the epilogue.
 // ------------------------------------------------------------------------------------------------------------
+// the flow loss's per-element term (dmcnet_hip.h: kind 0 = MSE, 1 = SmoothL1 with beta 1, 2 = L1) of d = out - flow, in double.
+// The kind is a COMPILE-TIME argument: the MSE / no-loss kernel is the instantiation KIND = 0, whose code is what it was before
+// the other kinds existed.
+template <int KIND>
+__device__ __forceinline__ double fz_loss_term(float d) {
+    if constexpr (KIND == 0) return (double)d * (double)d;
+    const float ad = fabsf(d);
+    // SmoothL1 without a branch: m = min(|d|, 1); m (|d| - m / 2) is |d| (|d| / 2) below 1 and |d| - 0.5 from 1 on, the bits of
+    // the two-branch form (halving is exact)
+    if constexpr (KIND == 1) { const float m = fminf(ad, 1.f); return (double)(m * (ad - 0.5f * m)); }
+    return (double)ad;
+}
+
 template <int K>
 struct FzG {
     static constexpr int CIN = cin_of(K), C = cout_of(K), NROW = 9 * C, NT = (NROW + 3) / 4, NA = (NT + 15) / 16;
@@ -144,7 +157,7 @@ struct FzLayer {
     f32x4 acc[NT];                    // one pixel per lane
     float b[CIN];                     // the step's B operands (channels [0, OLD) requested before the previous barrier)
     float bias[C];
-    double sq;                        // K == 5: sum of squared differences to the flow target
+    double sq;                        // K == 5: sum of the loss terms of (out - flow target)
     static constexpr bool ROT = G::ROT;
 
     __device__ __forceinline__ void load_weights(const ParamPtrs& prm, int lane) {
@@ -198,7 +211,7 @@ struct FzLayer {
     }
 
     // step t of the strip (phase J = t mod 3 for the rotating layers): consume input row t - 2K, complete output row t - 2K - 1
-    template <int J>
+    template <int J, int KIND>
     __device__ __forceinline__ void step(const FusedArgs& a, const Strip& st, const Half& h, float* lds, int t) {
         const int i = t - 2 * K, o = i - 1;
         const bool emit = o >= st.w0 && o < st.w1, keep = o >= st.s0 && o < st.s1;      // complete a row of the window / one the item stores
@@ -244,7 +257,7 @@ struct FzLayer {
 #pragma unroll
                 for (int co = 0; co < C; ++co) {
                     store_at(plane + co * hw, pix, v[co]);
-                    if (a.flow) { const float d = v[co] - flw[co]; sq += (double)d * (double)d; }
+                    if (a.flow) { const float d = v[co] - flw[co]; sq += fz_loss_term<KIND>(d); }
                 }
             }
         }
@@ -295,7 +308,7 @@ struct FzLayer<0> {
 #pragma unroll
         for (int ci = 1; ci < CIN; ++ci) tiles<0, false>(A[ci * 3 + DY], b[DY][ci]);
     }
-    template <int J>
+    template <int J, int KIND>
     __device__ __forceinline__ void step(const FusedArgs& a, const Strip& st, const Half& h, float* lds, int t) {
         const int o = t - 1;
         if (o < st.w0 || o >= st.w1) return;
@@ -337,7 +350,7 @@ struct FzLayer<0> {
 };
 
 // a wave that runs layer KA on pixel half hf (and, when KB >= 0, layer KB on half hfb after it)
-template <int KA, int KB>
+template <int KA, int KB, int KIND>
 __device__ __forceinline__ void run_layers(const FusedArgs& a, float* lds, int hf, int hfb, int lane, int wave) {
     FzProf prof;
     FzLayer<KA> la;
@@ -359,11 +372,11 @@ __device__ __forceinline__ void run_layers(const FusedArgs& a, float* lds, int h
             // a rotating layer: three steps per trip, one per phase (straight-line code: the accumulators never meet a phi)
 #pragma unroll 1
             for (int t = t0; t < t0 + steps; t += 3) {
-                prof.begin(); la.template step<0>(a, st, h, lds, t); prof.end();
+                prof.begin(); la.template step<0, KIND>(a, st, h, lds, t); prof.end();
                 step_barrier();
-                prof.begin(); la.template step<1>(a, st, h, lds, t + 1); prof.end();
+                prof.begin(); la.template step<1, KIND>(a, st, h, lds, t + 1); prof.end();
                 step_barrier();
-                prof.begin(); la.template step<2>(a, st, h, lds, t + 2); prof.end();
+                prof.begin(); la.template step<2, KIND>(a, st, h, lds, t + 2); prof.end();
                 step_barrier();
             }
         } else {
@@ -371,8 +384,8 @@ __device__ __forceinline__ void run_layers(const FusedArgs& a, float* lds, int h
 #pragma unroll 1
             for (int t = t0; t < t0 + steps; ++t) {
                 prof.begin();
-                la.template step<0>(a, st, h, lds, t);
-                if (KB >= 0) lb.template step<0>(a, st, hb, lds, t);
+                la.template step<0, KIND>(a, st, h, lds, t);
+                if (KB >= 0) lb.template step<0, KIND>(a, st, hb, lds, t);
                 prof.end();
                 step_barrier();
             }
@@ -437,8 +450,8 @@ __device__ __forceinline__ void run_loader(const FusedArgs& a, float* lds, int l
     prof.flush(a, wave, lane);
 }
 
-__global__ __launch_bounds__(FZ_THREADS) void gen_fused_kernel(FusedArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[FZ_LDS];
+template <int KIND>
+__device__ __forceinline__ void gen_fused_body(const FusedArgs& a, float* lds) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int i = threadIdx.x; i < FZ_LDS; i += FZ_THREADS) lds[i] = 0.f;      // (columns >= the strip width stay zero)
@@ -446,15 +459,28 @@ __global__ __launch_bounds__(FZ_THREADS) void gen_fused_kernel(FusedArgs a) {
     // waves w, w + 4, w + 8 share a SIMD (measured: HW_ID of tools/ubench/gen_fused_prof.hip).  Cost of a wave's step = 8 clocks per
     // MFMA + 4 per other vector instruction (they do not overlap); per SIMD: layer 2 twice + staging / 3, 3, 4 / 1, 1, 4 / 5, 5, 0 + 0
     switch (wave) {
-        case 0: case 4: run_layers<2, -1>(a, lds, wave >> 2, 0, lane, wave); break;
+        case 0: case 4: run_layers<2, -1, KIND>(a, lds, wave >> 2, 0, lane, wave); break;
         case 8: run_loader(a, lds, lane, wave); break;
-        case 1: case 5: run_layers<3, -1>(a, lds, wave >> 2, 0, lane, wave); break;
-        case 9: run_layers<4, -1>(a, lds, 0, 0, lane, wave); break;
-        case 2: case 6: run_layers<1, -1>(a, lds, wave >> 2, 0, lane, wave); break;
-        case 10: run_layers<4, -1>(a, lds, 1, 0, lane, wave); break;
-        case 3: case 7: run_layers<5, -1>(a, lds, wave >> 2, 0, lane, wave); break;
-        default: run_layers<0, 0>(a, lds, 0, 1, lane, wave); break;       // layer 0, both halves
+        case 1: case 5: run_layers<3, -1, KIND>(a, lds, wave >> 2, 0, lane, wave); break;
+        case 9: run_layers<4, -1, KIND>(a, lds, 0, 0, lane, wave); break;
+        case 2: case 6: run_layers<1, -1, KIND>(a, lds, wave >> 2, 0, lane, wave); break;
+        case 10: run_layers<4, -1, KIND>(a, lds, 1, 0, lane, wave); break;
+        case 3: case 7: run_layers<5, -1, KIND>(a, lds, wave >> 2, 0, lane, wave); break;
+        default: run_layers<0, 0, KIND>(a, lds, 0, 1, lane, wave); break;       // layer 0, both halves
     }
+}
+
+// KIND 0 (MSE, or no loss at all: a.flow == null) keeps the kernel's name and, instantiated from the same text, its code
+__global__ __launch_bounds__(FZ_THREADS) void gen_fused_kernel(FusedArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[FZ_LDS];
+    gen_fused_body<0>(a, lds);
+}
+// SmoothL1 / L1 in the layer-5 epilogue: instantiations of their own, so that nothing the MSE kernel executes depends on them
+template <int KIND>
+__global__ __launch_bounds__(FZ_THREADS) void gen_fused_loss_kernel(FusedArgs a) {
+    static_assert(KIND == 1 || KIND == 2, "kind 0 is gen_fused_kernel");
+    __shared__ __attribute__((aligned(16))) float lds[FZ_LDS];
+    gen_fused_body<KIND>(a, lds);
 }
 
 }  // namespace
@@ -471,8 +497,9 @@ bool gen_fused_supported(int H, int W) { return H >= 1 && W >= 1 && W <= 2 * (FZ
 int gen_fused_max_partials() { return 2 * fz_num_cus_hw(); }
 
 int gen_fused_fwd(const float* mv, const float* res, float* feat, float* out, const ParamPtrs& prm, const float* flow,
-                  double* mse_part, int* nparts, int N, int H, int W, int add_mv, hipStream_t s) {
+                  double* mse_part, int* nparts, int N, int H, int W, int add_mv, hipStream_t s, int kind) {
     if (!gen_fused_supported(H, W)) return fail(DMC_E_INVALID, "gen_fused_fwd: shape %d x %d not served", H, W);
+    if (kind < 0 || kind > 2) return fail(DMC_E_INVALID, "gen_fused_fwd: loss kind %d", kind);
     FusedArgs a;
     a.mv = mv; a.res = res; a.feat = feat; a.out = out; a.prm = prm;
     a.flow = flow && mse_part ? flow : nullptr;
@@ -488,7 +515,9 @@ int gen_fused_fwd(const float* mv, const float* res, float* feat, float* out, co
 #endif
     const int wgs = a.nitems < fz_num_cus() ? a.nitems : fz_num_cus();
     if (nparts) *nparts = a.flow ? 2 * wgs : 0;
-    gen_fused_kernel<<<wgs, FZ_THREADS, 0, s>>>(a);
+    if (kind == 0 || !a.flow) gen_fused_kernel<<<wgs, FZ_THREADS, 0, s>>>(a);
+    else if (kind == 1) gen_fused_loss_kernel<1><<<wgs, FZ_THREADS, 0, s>>>(a);
+    else gen_fused_loss_kernel<2><<<wgs, FZ_THREADS, 0, s>>>(a);
     return check_launch("gen_fused");
 }
 

@@ -2446,12 +2446,13 @@ size_t dmc_gen_tiny_partials_bytes(int N, int H, int W) {
     return (size_t)(wgrad_groups(N, H, W) + RED_CHUNKS) * WPART_MAX * sizeof(float);
 }
 
-// flow != null: also reduce sum((out - flow)^2) into mse_part (the fused kernel's epilogue); *fused_wgs receives
-// the number of partials written, 0 if the shape took a path without the fused epilogue
+// flow != null: also reduce sum(l(out - flow)) into mse_part (the fused kernel's epilogue; l = the term of loss `kind`,
+// dmcnet_hip.h); *fused_wgs receives the number of partials written, 0 if the shape took a path without the fused epilogue
+// (the layer-by-layer kernels reduce the MSE only)
 static int gen_tiny_fwd_impl(const float* mv, const float* res, const float* const* w,
                              const float* const* b, float* out, float* saved, float* workspace, int N,
                              int H, int W, int add_mv_delta, const float* flow, double* mse_part, int* fused_wgs,
-                             dmc_stream_t stream) {
+                             dmc_stream_t stream, int kind = 0) {
     if (!mv || !res || !w || !b || !out || !workspace)
         return fail(DMC_E_INVALID, "dmc_gen_tiny_fwd: null pointer");
     // saved == NULL (inference: nothing kept for a backward pass) is served by the one-launch forward only -- the layer-by-layer
@@ -2470,7 +2471,7 @@ static int gen_tiny_fwd_impl(const float* mv, const float* res, const float* con
             P.w[k] = w[k];
             P.b[k] = b[k];
         }
-        return gen_fused_fwd(mv, res, saved, out, P, flow, mse_part, fused_wgs, N, H, W, add_mv_delta, s);
+        return gen_fused_fwd(mv, res, saved, out, P, flow, mse_part, fused_wgs, N, H, W, add_mv_delta, s, kind);
     }
     int x3mask = option(OPT_GEN_X3);
     for (int K = 0; K < GX_LAYERS; ++K)
@@ -2510,7 +2511,7 @@ static int gen_tiny_fwd_impl(const float* mv, const float* res, const float* con
             ra.tiles_y = (H + PT_H - 1) / PT_H;
             ra.ntiles = ra.tiles_y * nn;
             const int wgs = ra.ntiles < num_cus() ? ra.ntiles : num_cus();
-            if (flow && mse_part && step >= N) {              // (one pass over all frames: one partial set)
+            if (flow && mse_part && step >= N && kind == 0) {     // (one pass over all frames: one partial set)
                 ra.a.mse_flow = flow; ra.a.mse_part = mse_part;
                 if (fused_wgs) *fused_wgs = wgs * P_CONS;
             }
@@ -2550,6 +2551,26 @@ int dmc_gen_tiny_fwd_mse(const float* mv, const float* res, const float* const* 
         return dmc_flow_mse_fwd(out, flow, loss_out, static_cast<float*>(mse_partials), numel, stream);
     gen_mse_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(static_cast<const double*>(mse_partials), wgs, loss_out, (double)numel);
     return check_launch("gen_mse_final");
+}
+
+int dmc_gen_tiny_fwd_loss(int kind, const float* mv, const float* res, const float* const* w, const float* const* b,
+                          const float* flow, float* out, float* saved, float* workspace, float* loss_out,
+                          void* mse_partials, int N, int H, int W, int add_mv_delta, dmc_stream_t stream) {
+    if (kind < 0 || kind > 2) return fail(DMC_E_INVALID, "dmc_gen_tiny_fwd_loss: kind %d (0 = MSE, 1 = SmoothL1, 2 = L1)", kind);
+    if (!mv || !res || !w || !b || !flow || !out || !workspace || !loss_out || !mse_partials)
+        return fail(DMC_E_INVALID, "dmc_gen_tiny_fwd_loss: null pointer");
+    if (N <= 0 || H <= 0 || W <= 0) return fail(DMC_E_INVALID, "dmc_gen_tiny_fwd_loss: bad shape");
+    if (kind == 0)      // the MSE entry itself: the same kernels, the same bits
+        return dmc_gen_tiny_fwd_mse(mv, res, w, b, flow, out, saved, workspace, loss_out, mse_partials, N, H, W, add_mv_delta, stream);
+    int wgs = 0;
+    int rc = gen_tiny_fwd_impl(mv, res, w, b, out, saved, workspace, N, H, W, add_mv_delta, flow,
+                               static_cast<double*>(mse_partials), &wgs, stream, kind);
+    if (rc) return rc;
+    const size_t numel = (size_t)N * 2 * H * W;
+    if (wgs == 0)       // a shape the one-launch forward does not serve: the streaming reduction over the `out` just written
+        return dmc_flow_loss_fwd(kind, out, flow, nullptr, loss_out, static_cast<float*>(mse_partials), numel, stream);
+    gen_mse_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(static_cast<const double*>(mse_partials), wgs, loss_out, (double)numel);
+    return check_launch("gen_loss_final");
 }
 
 int dmc_gen_tiny_bwd(const float* mv, const float* res, const float* const* w, const float* saved,

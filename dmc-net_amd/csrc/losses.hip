@@ -1,6 +1,8 @@
-// Flow-reconstruction MSE and TSN consensus + cross-entropy for gfx950.
+// Flow-reconstruction losses (MSE, SmoothL1, L1, plain or attention-weighted) and TSN consensus + cross-entropy for gfx950.
 //
 // Reference behaviour: nn.MSELoss()(gen_flow, input_flow)  code/dmcnet/train.py:167,245;
+// --loss-mse MSELoss | SmoothL1Loss | L1                     code/dmcnet/train.py:166-172;
+// criterion_mse(att * gen_flow, att * input_flow)            code/dmcnet/train.py:335, code/dmcnet_GAN/train.py:352;
 // output.view(-1,S,C).mean(1) + CrossEntropyLoss           code/dmcnet/train.py:239-241.
 #include <atomic>
 #include <string.h>
@@ -81,6 +83,113 @@ __global__ __launch_bounds__(256) void flow_mse_bwd_kernel(const float* __restri
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (size_t i = n4 * 4; i < numel; ++i) ga[i] = (a[i] - b[i]) * scale;
+}
+
+// ---- the general flow loss: kind 0 = MSE, 1 = SmoothL1 (beta 1), 2 = L1; optionally attention-weighted ----------------
+// d = att * gen - att * flow with BOTH products rounded to fp32 before the subtraction, as the reference's two tensor
+// products are: a contraction into fma(att, gen, -(att * flow)) would keep one product exact, move d by an ulp and could
+// flip a SmoothL1 branch at |d| = 1.  Guaranteed twice: the products are __fmul_rn (an intrinsic the compiler never
+// contracts) and the whole library is compiled with -ffp-contract=off (build.py).
+template <bool ATT>
+__device__ __forceinline__ float loss_diff(float g, float f, float t) {
+    return ATT ? __fsub_rn(__fmul_rn(t, g), __fmul_rn(t, f)) : g - f;
+}
+template <int KIND>
+__device__ __forceinline__ float loss_term(float d) {
+    if constexpr (KIND == 0) return d * d;
+    const float ad = fabsf(d);
+    if constexpr (KIND == 1) return ad < 1.f ? 0.5f * d * d : ad - 0.5f;
+    return ad;
+}
+// l'(d); sign(0) = 0
+template <int KIND>
+__device__ __forceinline__ float loss_deriv(float d) {
+    const float sg = (float)(d > 0.f) - (float)(d < 0.f);
+    if constexpr (KIND == 0) return 2.f * d;
+    if constexpr (KIND == 1) return fabsf(d) < 1.f ? d : sg;
+    return sg;
+}
+
+// flow_mse_partial_kernel's scheme (16 B per lane per load, grid-stride, fp32 per-lane partials promoted to double, fixed order)
+template <int KIND, bool ATT>
+__global__ __launch_bounds__(256) void flow_loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                const float* __restrict__ t, double* __restrict__ partials,
+                                                                size_t numel) {
+    __shared__ double sm[4];
+    const size_t n4 = numel / 4;
+    const float4* a4 = reinterpret_cast<const float4*>(a);
+    const float4* b4 = reinterpret_cast<const float4*>(b);
+    const float4* t4 = reinterpret_cast<const float4*>(t);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const float4 x = a4[i], y = b4[i];
+        float4 w = make_float4(1.f, 1.f, 1.f, 1.f);
+        if constexpr (ATT) w = t4[i];
+        s0 += loss_term<KIND>(loss_diff<ATT>(x.x, y.x, w.x));
+        s1 += loss_term<KIND>(loss_diff<ATT>(x.y, y.y, w.y));
+        s2 += loss_term<KIND>(loss_diff<ATT>(x.z, y.z, w.z));
+        s3 += loss_term<KIND>(loss_diff<ATT>(x.w, y.w, w.w));
+    }
+    double s = (double)s0 + (double)s1 + (double)s2 + (double)s3;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (size_t i = n4 * 4; i < numel; ++i) s += (double)loss_term<KIND>(loss_diff<ATT>(a[i], b[i], ATT ? t[i] : 1.f));
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+}
+
+// g = l'(d) * (*grad_loss / numel); grad_gen = g * att (or g); grad_att = gen * g - flow * g (the reference's gradient reaches
+// att through both products; each product rounded, as autograd's two contributions are)
+template <int KIND, bool ATT, bool GATT>
+__global__ __launch_bounds__(256) void flow_loss_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                            const float* __restrict__ t, const float* __restrict__ grad_loss,
+                                                            float* __restrict__ ga, float* __restrict__ gt, size_t numel) {
+    const float scale = (*grad_loss) / (float)numel;
+    const size_t n4 = numel / 4;
+    const float4* a4 = reinterpret_cast<const float4*>(a);
+    const float4* b4 = reinterpret_cast<const float4*>(b);
+    const float4* t4 = reinterpret_cast<const float4*>(t);
+    float4* ga4 = reinterpret_cast<float4*>(ga);
+    float4* gt4 = reinterpret_cast<float4*>(gt);
+    auto one = [&](float x, float y, float w, float& gx, float& gw) {
+        const float g = loss_deriv<KIND>(loss_diff<ATT>(x, y, w)) * scale;
+        gx = ATT ? __fmul_rn(g, w) : g;
+        if constexpr (GATT) gw = __fsub_rn(__fmul_rn(x, g), __fmul_rn(y, g));
+    };
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const float4 x = a4[i], y = b4[i];
+        float4 w = make_float4(1.f, 1.f, 1.f, 1.f), gx, gw;
+        if constexpr (ATT) w = t4[i];
+        one(x.x, y.x, w.x, gx.x, gw.x);
+        one(x.y, y.y, w.y, gx.y, gw.y);
+        one(x.z, y.z, w.z, gx.z, gw.z);
+        one(x.w, y.w, w.w, gx.w, gw.w);
+        ga4[i] = gx;
+        if constexpr (GATT) gt4[i] = gw;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (size_t i = n4 * 4; i < numel; ++i) {
+            float gx, gw;
+            one(a[i], b[i], ATT ? t[i] : 1.f, gx, gw);
+            ga[i] = gx;
+            if constexpr (GATT) gt[i] = gw;
+        }
+}
+
+template <int KIND>
+int launch_flow_loss_partial(const float* a, const float* b, const float* t, double* part, size_t numel, int blocks, hipStream_t s) {
+    if (t) flow_loss_partial_kernel<KIND, true><<<blocks, 256, 0, s>>>(a, b, t, part, numel);
+    else flow_loss_partial_kernel<KIND, false><<<blocks, 256, 0, s>>>(a, b, t, part, numel);
+    return check_launch("flow_loss_partial");
+}
+template <int KIND>
+int launch_flow_loss_bwd(const float* a, const float* b, const float* t, const float* gl, float* ga, float* gt, size_t numel,
+                         int blocks, hipStream_t s) {
+    if (t && gt) flow_loss_bwd_kernel<KIND, true, true><<<blocks, 256, 0, s>>>(a, b, t, gl, ga, gt, numel);
+    else if (t) flow_loss_bwd_kernel<KIND, true, false><<<blocks, 256, 0, s>>>(a, b, t, gl, ga, gt, numel);
+    else flow_loss_bwd_kernel<KIND, false, false><<<blocks, 256, 0, s>>>(a, b, t, gl, ga, gt, numel);
+    return check_launch("flow_loss_bwd");
 }
 
 // One workgroup of 16 waves; wave w handles clips w, w+16, ...; lanes cover the classes.
@@ -190,6 +299,41 @@ int dmc_flow_mse_bwd(const float* gen_flow, const float* flow, const float* grad
     const int blocks = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
     flow_mse_bwd_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(gen_flow, flow, grad_loss, grad_gen, numel);
     return check_launch("flow_mse_bwd");
+}
+
+size_t dmc_flow_loss_partials_bytes(void) { return dmc_flow_mse_partials_bytes(); }
+
+int dmc_flow_loss_fwd(int kind, const float* gen_flow, const float* flow, const float* att, float* loss_out, float* partials,
+                      size_t numel, dmc_stream_t stream) {
+    if (kind < 0 || kind > 2) return fail(DMC_E_INVALID, "dmc_flow_loss_fwd: kind %d (0 = MSE, 1 = SmoothL1, 2 = L1)", kind);
+    if (!gen_flow || !flow || !loss_out || !partials || numel == 0)
+        return fail(DMC_E_INVALID, "dmc_flow_loss_fwd: null pointer or empty tensor");
+    if (kind == 0 && !att) return dmc_flow_mse_fwd(gen_flow, flow, loss_out, partials, numel, stream);     // the same kernels: the same bits
+    hipStream_t s = (hipStream_t)stream;
+    size_t want = (numel / 4 + 255) / 256;
+    const int blocks = (int)(want < 1 ? 1 : (want > MSE_BLOCKS ? MSE_BLOCKS : want));
+    double* part = (double*)partials;
+    int rc = kind == 0 ? launch_flow_loss_partial<0>(gen_flow, flow, att, part, numel, blocks, s)
+           : kind == 1 ? launch_flow_loss_partial<1>(gen_flow, flow, att, part, numel, blocks, s)
+                       : launch_flow_loss_partial<2>(gen_flow, flow, att, part, numel, blocks, s);
+    if (rc) return rc;
+    flow_mse_final_kernel<<<1, 256, 0, s>>>(part, blocks, loss_out, numel);
+    return check_launch("flow_loss_final");
+}
+
+int dmc_flow_loss_bwd(int kind, const float* gen_flow, const float* flow, const float* att, const float* grad_loss,
+                      float* grad_gen, float* grad_att, size_t numel, dmc_stream_t stream) {
+    if (kind < 0 || kind > 2) return fail(DMC_E_INVALID, "dmc_flow_loss_bwd: kind %d (0 = MSE, 1 = SmoothL1, 2 = L1)", kind);
+    if (!gen_flow || !flow || !grad_loss || !grad_gen || numel == 0)
+        return fail(DMC_E_INVALID, "dmc_flow_loss_bwd: null pointer or empty tensor");
+    if (grad_att && !att) return fail(DMC_E_INVALID, "dmc_flow_loss_bwd: grad_att given without att");
+    if (kind == 0 && !att) return dmc_flow_mse_bwd(gen_flow, flow, grad_loss, grad_gen, numel, stream);    // the same kernel: the same bits
+    hipStream_t s = (hipStream_t)stream;
+    size_t want = (numel / 4 + 255) / 256;
+    const int blocks = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    return kind == 0 ? launch_flow_loss_bwd<0>(gen_flow, flow, att, grad_loss, grad_gen, grad_att, numel, blocks, s)
+         : kind == 1 ? launch_flow_loss_bwd<1>(gen_flow, flow, att, grad_loss, grad_gen, grad_att, numel, blocks, s)
+                     : launch_flow_loss_bwd<2>(gen_flow, flow, att, grad_loss, grad_gen, grad_att, numel, blocks, s);
 }
 
 int dmc_consensus_ce_fwd_bwd(const float* logits, const int64_t* target, float* consensus,

@@ -79,6 +79,12 @@ class EstimatorDenseNetTiny(DenseEstimatorBase):
         ws, bs = self._params()
         return ops.gen_tiny_mse(mv, res, flow, ws, bs, add_mv)
 
+    def forward_mv_res_loss(self, kind, mv, res, flow, add_mv=False):
+        """(gen_flow, criterion(gen_flow, flow)) for ``kind`` = "MSELoss" | "SmoothL1Loss" | "L1" (code/dmcnet/train.py:166-172):
+        the loss is reduced in the forward's last kernel."""
+        ws, bs = self._params()
+        return ops.gen_tiny_loss(kind, mv, res, flow, ws, bs, add_mv)
+
     def forward(self, x):
         return self.forward_mv_res(x[:, :2].contiguous(), x[:, 2:].contiguous(), False)
 
@@ -144,7 +150,10 @@ class ContextNetworkAtt(nn.Module):
         plan = ((ch_in, 32, 1), (32, 128, 2), (128, 128, 4), (128, 96, 8), (96, 64, d5), (64, 32, 1))
         self.conv_context = nn.Sequential(*[_dilated_unit(a, b, d, batch_norm) for a, b, d in plan])
         self.predict_flow = _dilated_unit(32, 2, 1, batch_norm)
-        self.predict_att = nn.Sequential(_dilated_unit(32, 2, 1, batch_norm), nn.ReLU(inplace=True))
+        # (the reference's ReLU is in-place on the in-place LeakyReLU's result, which that LeakyReLU's backward needs: autograd
+        # refuses the attention gradient, "modified by an inplace operation".  Out of place: the same values, the same gradient
+        # -- where the ReLU cuts, its own backward passes zero -- and the attention-weighted loss can be trained)
+        self.predict_att = nn.Sequential(_dilated_unit(32, 2, 1, batch_norm), nn.ReLU(inplace=False))
 
     def forward(self, x):
         x = self.conv_context(x)
@@ -390,6 +399,25 @@ class Model(nn.Module):
             return self.base_model(gen_flow.detach()), gen_flow, loss_mse
         base_out, gen_flow = self.forward(input_mv, input_residual)
         return base_out, gen_flow, ops.flow_mse(gen_flow, flow)
+
+    def forward_with_flow_loss(self, kind, input_mv, input_residual, input_flow):
+        """The general form of ``forward_with_flow_mse``: ``kind`` is the reference's ``--loss-mse`` ("MSELoss" |
+        "SmoothL1Loss" | "L1", code/dmcnet/train.py:166-172).  "MSELoss" IS forward_with_flow_mse; the other two are reduced
+        in the generator's last kernel under the same conditions and by ops.flow_loss otherwise."""
+        if kind == "MSELoss":
+            return self.forward_with_flow_mse(input_mv, input_residual, input_flow)
+        if kind not in ops.FLOW_LOSS_KINDS:
+            raise ValueError("flow loss must be one of %s, got %r" % (tuple(ops.FLOW_LOSS_KINDS), kind))
+        if self.arch_d is not None or self.att == 1:
+            raise TypeError("forward_with_flow_loss serves the dmcnet variant without attention")
+        flow = input_flow.reshape((-1,) + tuple(input_flow.shape[-3:]))
+        if isinstance(self.gen_flow_model, EstimatorDenseNetTiny) and self.gen_flow_ds_factor == 0:
+            mv = input_mv.reshape((-1,) + tuple(input_mv.shape[-3:]))
+            res = input_residual.reshape((-1,) + tuple(input_residual.shape[-3:]))
+            gen_flow, loss = self.gen_flow_model.forward_mv_res_loss(kind, mv, res, flow, add_mv=self.gen_flow_or_delta == 1)
+            return self.base_model(gen_flow.detach()), gen_flow, loss
+        base_out, gen_flow = self.forward(input_mv, input_residual)
+        return base_out, gen_flow, ops.flow_loss(kind, gen_flow, flow)
 
     @property
     def crop_size(self):

@@ -5,7 +5,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["gen_tiny", "flow_mse", "consensus_ce", "disc_tail", "bn_act", "bn_act_supported", "prepare_inputs",
+__all__ = ["gen_tiny", "flow_mse", "flow_loss", "gen_tiny_loss", "FLOW_LOSS_KINDS", "consensus_ce", "disc_tail", "bn_act", "bn_act_supported", "prepare_inputs",
            "u8_frames_buffer", "conv_nhwc", "conv_nhwc_supported", "disc_block", "disc_block_supported"]
 
 
@@ -212,6 +212,85 @@ def gen_tiny_mse(mv, res, flow, weights, biases, add_mv=False):
     return _GenTinyMSE.apply(mv, res, flow, bool(add_mv), *weights, *biases)
 
 
+#: ``--loss-mse`` name (code/dmcnet/train.py:166-172) -> the C ABI's loss kind
+FLOW_LOSS_KINDS = {"MSELoss": 0, "SmoothL1Loss": 1, "L1": 2}
+
+
+def _loss_kind(kind_name):
+    if kind_name not in FLOW_LOSS_KINDS:
+        raise ValueError("flow loss must be one of %s, got %r" % (tuple(FLOW_LOSS_KINDS), kind_name))
+    return FLOW_LOSS_KINDS[kind_name]
+
+
+class _GenTinyLoss(torch.autograd.Function):
+    """_GenTinyMSE with the criterion chosen: (gen_flow, criterion_mse(gen_flow, flow)) for ``--loss-mse`` MSELoss /
+    SmoothL1Loss / L1 (code/dmcnet/train.py:166-172,245), the loss reduced in the epilogue of the kernel that writes
+    gen_flow (dmc_gen_tiny_fwd_loss).  Backward = dmc_flow_loss_bwd's gradient (plus whatever else reaches gen_flow)
+    through the generator's backward."""
+
+    @staticmethod
+    def forward(ctx, kind, mv, res, flow, add_mv, *params):
+        lib = _lib.load()
+        _need_cuda(mv, res, flow, *params)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            raise NotImplementedError("no gradients w.r.t. the MV / residual / flow inputs")
+        mv, res, flow = mv.contiguous(), res.contiguous(), flow.contiguous()
+        ws, bs = [p.contiguous() for p in params[:6]], [p.contiguous() for p in params[6:]]
+        n, _, h, w = mv.shape
+        if tuple(flow.shape) != (n, 2, h, w):
+            raise ValueError("flow target %s does not match the generator output %s" % (tuple(flow.shape), (n, 2, h, w)))
+        out = torch.empty((n, 2, h, w), dtype=torch.float32, device=mv.device)
+        loss = torch.empty((), dtype=torch.float32, device=mv.device)
+        saved = _floats(lib.dmc_gen_tiny_saved_bytes(n, h, w), mv.device)
+        work = _floats(lib.dmc_gen_tiny_workspace_bytes(), mv.device)
+        part = _floats(lib.dmc_gen_tiny_mse_partials_bytes(), mv.device)
+        with _span("gen_tiny_fwd"):
+            _lib.check(lib.dmc_gen_tiny_fwd_loss(kind, _lib.ptr(mv), _lib.ptr(res), _lib.ptr_array(ws), _lib.ptr_array(bs),
+                                                 _lib.ptr(flow), _lib.ptr(out), _lib.ptr(saved), _lib.ptr(work),
+                                                 _lib.ptr(loss), _lib.ptr(part), n, h, w, int(add_mv), _stream()),
+                       "dmc_gen_tiny_fwd_loss")
+        ctx.kind = kind
+        ctx.save_for_backward(mv, res, saved, out, flow, *ws)
+        ctx.bias_like = [(b.shape, b.dtype) for b in bs]
+        ctx.set_materialize_grads(False)
+        return out, loss
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_loss):
+        lib = _lib.load()
+        mv, res, saved, out, flow = ctx.saved_tensors[:5]
+        ws = list(ctx.saved_tensors[5:])
+        n, _, h, w = mv.shape
+        g = None
+        if grad_loss is not None:
+            g = torch.empty_like(out)
+            with _span("flow_loss_bwd"):
+                _lib.check(lib.dmc_flow_loss_bwd(ctx.kind, _lib.ptr(out), _lib.ptr(flow), None,
+                                                 _lib.ptr(grad_loss.contiguous().float()), _lib.ptr(g), None, out.numel(),
+                                                 _stream()), "dmc_flow_loss_bwd")
+        if grad_out is not None:
+            g = grad_out.contiguous() if g is None else g.add_(grad_out)
+        if g is None:
+            return (None,) * (5 + 12)
+        dws = [torch.empty_like(x) for x in ws]
+        dbs = [torch.empty(s, dtype=d, device=mv.device) for s, d in ctx.bias_like]
+        gbuf = _floats(lib.dmc_gen_tiny_gbuf_bytes(n, h, w), mv.device)
+        partials = _floats(lib.dmc_gen_tiny_partials_bytes(n, h, w), mv.device)
+        work = _floats(lib.dmc_gen_tiny_workspace_bytes(), mv.device)
+        with _span("gen_tiny_bwd"):
+            _lib.check(lib.dmc_gen_tiny_bwd(_lib.ptr(mv), _lib.ptr(res), _lib.ptr_array(ws), _lib.ptr(saved),
+                                            _lib.ptr(g), _lib.ptr_array(dws), _lib.ptr_array(dbs), _lib.ptr(gbuf),
+                                            _lib.ptr(partials), _lib.ptr(work), n, h, w, _stream()),
+                       "dmc_gen_tiny_bwd")
+        return (None, None, None, None, None) + tuple(dws) + tuple(dbs)
+
+
+def gen_tiny_loss(kind_name, mv, res, flow, weights, biases, add_mv=False):
+    """(gen_flow [N,2,H,W], criterion(gen_flow, flow)) in one forward launch sequence; kind_name: "MSELoss" (what
+    gen_tiny_mse gives, bit for bit), "SmoothL1Loss" or "L1" (see _GenTinyLoss)."""
+    return _GenTinyLoss.apply(_loss_kind(kind_name), mv, res, flow, bool(add_mv), *weights, *biases)
+
+
 def gen_tiny(mv, res, weights, biases, add_mv=False):
     """mv [N,2,H,W], res [N,3,H,W], 6 weights + 6 biases (reference layout) -> [N,2,H,W]."""
     return _GenTiny.apply(mv, res, bool(add_mv), torch.is_grad_enabled(), *weights, *biases)
@@ -253,6 +332,57 @@ class _FlowMSE(torch.autograd.Function):
 
 def flow_mse(gen_flow, flow):
     return _FlowMSE.apply(gen_flow, flow)
+
+
+class _FlowLoss(torch.autograd.Function):
+    """criterion_mse(gen_flow, input_flow) for nn.MSELoss / nn.SmoothL1Loss / nn.L1Loss (code/dmcnet/train.py:166-172,245)
+    and its attention-weighted form criterion_mse(att * gen_flow, att * input_flow) (code/dmcnet/train.py:335,
+    code/dmcnet_GAN/train.py:352): one pass forward, one pass backward, the two products never materialised."""
+
+    @staticmethod
+    def forward(ctx, kind, gen_flow, flow, att):
+        lib = _lib.load()
+        _need_cuda(gen_flow, flow, att)
+        if ctx.needs_input_grad[2]:
+            raise NotImplementedError("no gradient w.r.t. the flow target")
+        if gen_flow.shape != flow.shape or (att is not None and att.shape != gen_flow.shape):
+            raise ValueError("shape mismatch %s vs %s%s" % (tuple(gen_flow.shape), tuple(flow.shape),
+                                                            "" if att is None else " vs att %s" % (tuple(att.shape),)))
+        for t in (gen_flow, flow, att):
+            if t is not None and t.dtype != torch.float32:
+                raise _lib.DmcHipError("expected fp32 tensors, got %s" % t.dtype)
+        gen_flow, flow = gen_flow.contiguous(), flow.contiguous()
+        att = None if att is None else att.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=gen_flow.device)
+        partials = _floats(lib.dmc_flow_loss_partials_bytes(), gen_flow.device)
+        with _span("flow_loss_fwd"):
+            _lib.check(lib.dmc_flow_loss_fwd(kind, _lib.ptr(gen_flow), _lib.ptr(flow), _lib.ptr(att), _lib.ptr(loss),
+                                             _lib.ptr(partials), gen_flow.numel(), _stream()),
+                       "dmc_flow_loss_fwd")
+        ctx.kind, ctx.has_att = kind, att is not None
+        ctx.want_att = att is not None and ctx.needs_input_grad[3]
+        ctx.save_for_backward(*((gen_flow, flow) + ((att,) if att is not None else ())))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        lib = _lib.load()
+        gen_flow, flow = ctx.saved_tensors[:2]
+        att = ctx.saved_tensors[2] if ctx.has_att else None
+        grad_loss = grad_loss.contiguous().float()
+        grad = torch.empty_like(gen_flow)
+        grad_att = torch.empty_like(att) if ctx.want_att else None
+        with _span("flow_loss_bwd"):
+            _lib.check(lib.dmc_flow_loss_bwd(ctx.kind, _lib.ptr(gen_flow), _lib.ptr(flow), _lib.ptr(att), _lib.ptr(grad_loss),
+                                             _lib.ptr(grad), _lib.ptr(grad_att), gen_flow.numel(), _stream()),
+                       "dmc_flow_loss_bwd")
+        return None, grad, None, grad_att
+
+
+def flow_loss(kind_name, gen_flow, flow, att=None):
+    """The reference's reconstruction criterion on the device: kind_name "MSELoss" | "SmoothL1Loss" | "L1"; att (optional,
+    the shape of gen_flow) weights both arguments.  Gradients to gen_flow and att, none to flow."""
+    return _FlowLoss.apply(_loss_kind(kind_name), gen_flow, flow, att)
 
 
 class _ConsensusCE(torch.autograd.Function):

@@ -153,12 +153,19 @@ FLOW_LOSSES = ("MSELoss", "SmoothL1Loss", "L1")
 
 
 def flow_loss(kind, gen_flow, flow, att_flow=None):
-    """``criterion_mse`` of the reference (``--loss_mse``, code/dmcnet/train.py:166-172): MSELoss is
-    the HIP kernel (every shipped recipe); SmoothL1Loss / L1 and the attention-weighted form
-    ``criterion(att * gen, att * flow)`` (code/dmcnet/train.py:335, code/dmcnet_GAN/train.py:352),
-    whose gradient also reaches ``att`` through the target, run on the stock PyTorch-ROCm ops."""
+    """``criterion_mse`` of the reference (``--loss_mse``, code/dmcnet/train.py:166-172) and its
+    attention-weighted form ``criterion(att * gen, att * flow)`` (code/dmcnet/train.py:335,
+    code/dmcnet_GAN/train.py:352), whose gradient also reaches ``att`` through the target.  Device
+    tensors: plain MSELoss is ops.flow_mse (every shipped recipe), every other combination
+    ops.flow_loss (one pass, the two products never written).  CPU tensors: the stock ops."""
     if kind not in FLOW_LOSSES:
         raise ValueError("loss_mse must be one of %s, got %r" % (FLOW_LOSSES, kind))
+    if gen_flow.is_cuda:
+        if att_flow is None and kind == "MSELoss":
+            return ops.flow_mse(gen_flow, flow)
+        if att_flow is not None and att_flow.shape != gen_flow.shape:
+            att_flow = att_flow.expand_as(gen_flow)
+        return ops.flow_loss(kind, gen_flow, flow, att_flow)
     if att_flow is not None:
         gen_flow, flow = att_flow * gen_flow, att_flow * flow
     elif kind == "MSELoss":
@@ -193,6 +200,10 @@ class DmcnetTrainStep(object):
         if self.loss_mse == "MSELoss" and self.att == 0 and hasattr(self.model, "forward_with_flow_mse"):
             # the MSE is reduced in the epilogue of the kernel that writes gen_flow (no re-read of it)
             output, gen_flow, loss_mse = self.model.forward_with_flow_mse(input_mv, input_residual, flow)
+            loss_cls, consensus = ops.consensus_ce(output, target, self.num_segments)
+        elif self.att == 0 and flow.is_cuda and hasattr(self.model, "forward_with_flow_loss"):
+            # SmoothL1Loss / L1: the same epilogue, the kind's own instantiation of the kernel
+            output, gen_flow, loss_mse = self.model.forward_with_flow_loss(self.loss_mse, input_mv, input_residual, flow)
             loss_cls, consensus = ops.consensus_ce(output, target, self.num_segments)
         else:
             outs = self.model(input_mv, input_residual)

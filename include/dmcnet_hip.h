@@ -113,13 +113,27 @@ int dmc_gen_tiny_fwd(const float* mv, const float* res, const float* const* w,
  * *loss_out = mean((out - flow)^2) = nn.MSELoss()(gen_flow, input_flow), code/dmcnet/train.py:167,245,
  * reduced in the epilogue of the kernel that produces `out` (the separate loss kernel would read `out`
  * back from HBM).  flow [N,2,H,W]; loss_out: one float on the device; mse_partials: workspace of
- * dmc_gen_tiny_mse_partials_bytes().  Shapes that do not take the fused kernel (W % 4 != 0, W > 224)
- * fall back to dmc_flow_mse_fwd internally.  The gradient is dmc_flow_mse_bwd's, unchanged.
+ * dmc_gen_tiny_mse_partials_bytes().  Shapes that do not reach a kernel with the loss epilogue (W > 224; with option
+ * "gen_fused" 0 also W % 4 != 0) fall back to dmc_flow_mse_fwd internally.  The gradient is dmc_flow_mse_bwd's, unchanged.
  */
 size_t dmc_gen_tiny_mse_partials_bytes(void);
 int dmc_gen_tiny_fwd_mse(const float* mv, const float* res, const float* const* w, const float* const* b,
                          const float* flow, float* out, float* saved, float* workspace, float* loss_out,
                          void* mse_partials, int N, int H, int W, int add_mv_delta, dmc_stream_t stream);
+
+/*
+ * The same with the loss kind chosen (--loss-mse MSELoss | SmoothL1Loss | L1, code/dmcnet/train.py:166-172, applied as
+ * criterion_mse(gen_flow, input_flow), code/dmcnet/train.py:245): kind 0 = MSE, 1 = SmoothL1 (beta 1), 2 = L1, the terms
+ * of dmc_flow_loss_fwd below.  The layer-5 epilogue of the one-launch forward accumulates l(out - flow) in the same double
+ * accumulators and partial layout (mse_partials: dmc_gen_tiny_mse_partials_bytes()); the kind is a compile-time argument
+ * of that kernel, and kind 0 IS dmc_gen_tiny_fwd_mse (same kernels, same bits).  Shapes the one-launch forward does not
+ * serve (W > 224, option "gen_fused" 0) fall back to dmc_flow_loss_fwd internally.  No attention form: the attention
+ * estimator is not this generator.  The gradient is dmc_flow_loss_bwd's.  kind outside 0 .. 2, a NULL pointer (saved
+ * excepted, as for dmc_gen_tiny_fwd) or a non-positive size: DMC_E_INVALID before any launch.
+ */
+int dmc_gen_tiny_fwd_loss(int kind, const float* mv, const float* res, const float* const* w, const float* const* b,
+                          const float* flow, float* out, float* saved, float* workspace, float* loss_out,
+                          void* mse_partials, int N, int H, int W, int add_mv_delta, dmc_stream_t stream);
 
 /* Bytes of the gradient-feature buffer (`gbuf`) and of the per-workgroup weight-gradient
  * partials (`partials`) that the backward needs. */
@@ -149,6 +163,32 @@ int dmc_flow_mse_fwd(const float* gen_flow, const float* flow, float* loss_out, 
 /* grad_gen = 2 (gen - flow) / numel * (*grad_loss) ; grad_loss is a device scalar. */
 int dmc_flow_mse_bwd(const float* gen_flow, const float* flow, const float* grad_loss,
                      float* grad_gen, size_t numel, dmc_stream_t stream);
+
+/* ---- flow reconstruction loss, every criterion of the reference ------------------------------
+ * Replaces: criterion_mse = nn.MSELoss() | nn.SmoothL1Loss() | nn.L1Loss()   (--loss-mse, code/dmcnet/train.py:166-172)
+ *           criterion_mse(gen_flow, input_flow)                               code/dmcnet/train.py:245
+ *           criterion_mse(att_flow * gen_flow, att_flow * input_flow)         code/dmcnet/train.py:335,
+ *                                                                             code/dmcnet_GAN/train.py:352
+ * kind: 0 = MSE, 1 = SmoothL1 (beta 1), 2 = L1.  att: NULL (plain form) or [numel] weights.  In fp32:
+ *   x = att ? att * gen : gen,  y = att ? att * flow : flow  (each product rounded before the subtraction),  d = x - y,
+ *   l(d)  = d^2            | (|d| < 1 ? 0.5 d^2 : |d| - 0.5) | |d|,
+ *   l'(d) = 2 d            | (|d| < 1 ? d : sign(d))         | sign(d), sign(0) = 0,
+ *   *loss_out = mean of l(d) over all `numel` elements.
+ * One streaming pass (16-byte loads: every array 16-byte aligned), per-lane partials promoted to double, every sum in a
+ * fixed order: no atomics, repeated runs are bit-identical.  partials: workspace of dmc_flow_loss_partials_bytes().
+ * kind 0 without att runs dmc_flow_mse_fwd / _bwd's kernels and gives their bits.
+ * DMC_E_INVALID before any launch (nothing written): kind outside 0 .. 2, a NULL pointer (att / grad_att excepted),
+ * numel == 0, grad_att given without att.
+ */
+size_t dmc_flow_loss_partials_bytes(void);
+int dmc_flow_loss_fwd(int kind, const float* gen_flow, const float* flow, const float* att, float* loss_out,
+                      float* partials, size_t numel, dmc_stream_t stream);
+/* The gradient of the above for the upstream gradient *grad_loss (a device scalar), one pass: with s = *grad_loss / numel,
+ *   grad_gen = l'(d) s (att or 1),   grad_att = gen (l'(d) s) - flow (l'(d) s)   (the reference's gradient reaches att
+ * through both products, code/dmcnet/train.py:335); grad_att may be NULL (not wanted) and must be NULL when att is NULL.
+ * There is no gradient to flow. */
+int dmc_flow_loss_bwd(int kind, const float* gen_flow, const float* flow, const float* att, const float* grad_loss,
+                      float* grad_gen, float* grad_att, size_t numel, dmc_stream_t stream);
 
 /* ---- TSN segment consensus + cross entropy ---------------------------------------------------
  * Replaces: output.view(-1, S, C).mean(dim=1); CrossEntropyLoss()(output, target)
