@@ -7,8 +7,6 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libdmcnet_hip.so")
-#: gen_fused_bwd.hip (the one-launch generator data gradient: measured slower) is part of the --measure build only
-MEASURE_ONLY = ["gen_fused_bwd.hip"]
 SOURCES = ["gen_tiny.hip", "gen_x3.hip", "gen_fused.hip", "gen_wgrad.hip", "losses.hip", "disc_tail.hip", "bn_act.hip", "prepare.hip", "clip_prep.hip", "stem.hip", "conv_nhwc.hip", "conv_small.hip", "conv_x3s.hip", "conv_x3q.hip", "disc_first.hip", "conv3d_bf16.hip", "pool3d_bf16.hip", "bn3d_bf16.hip", "stem3d_bf16.hip", "unit3d.hip", "coviar_post.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -103,7 +101,7 @@ def build_library(force=False, verbose=False, measure=False):
 
 def _build_measure(verbose):
     objs = []
-    for src in SOURCES + MEASURE_ONLY:
+    for src in SOURCES:
         path = os.path.join(CSRC, src)
         obj = os.path.join(CSRC, "measure_" + src.replace(".hip", ".o"))
         objs.append(obj)

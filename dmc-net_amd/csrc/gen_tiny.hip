@@ -469,20 +469,13 @@ constexpr int RING = 3;                             // chunk buffers: one comput
 constexpr int RING_DMA = LCH * P_ROWS;              // 40 row transfers per chunk, all by the producer
 static_assert(RING_DMA <= 63, "vmcnt is a 6-bit counter");
 
-// Tile geometry of the ring kernels.  HALF = false: 8-row tiles, four pixels per lane, one 8-wave workgroup per CU (the
-// default).  HALF = true (measurement variant, option gen_layer_path = 3, forward layers 2 and 3): 4-row tiles, TWO
-// pixels per lane -- 7 consumer waves x 128 pixels = 4 x 224 -- with the ring sized by the layer's chunk, so that two
-// workgroups fit a CU (<= 80 KB each, <= 128 VGPRs) and their push epilogues fall out of phase (round-2 verdict, variant ii).
-// VAR = 2 (measurement variant iii, option gen_layer_path = 4, forward layer 2): the default tile, but a TWO-stage ring sized by
-// the layer's chunk (61 KB + weights), so that two workgroups fit a CU with full-width accesses and no extra halo rows.
+// Ring geometry.  VAR = 0: 8-row tiles, four pixels per lane, a three-stage ring, one 8-wave workgroup per CU.  VAR = 2
+// (forward layer 2): the same tile, but a TWO-stage ring sized by the layer's chunk (61 KB + weights), so that two workgroups
+// fit a CU.  (VAR = 1, 4-row tiles with two pixels per lane, lost its measurement and is removed: DESIGN 1, profiles/r3_gen_variant_ii.txt.)
 template <int VAR>
 struct RingGeo {
-    static constexpr bool HALF = VAR == 1;
-    static constexpr int ROWS = HALF ? 4 : PT_H;            // tile rows
-    static constexpr int SEGS = HALF ? 2 : M_SEGS;          // consecutive pixels per lane
     static constexpr int STAGES = VAR == 2 ? 2 : RING;      // chunk buffers of the ring
-    static constexpr int SROWS = ROWS + 2;                  // staged rows per channel
-    static constexpr int PLANE = SROWS * LTW;               // floats per staged channel
+    static constexpr int PLANE = P_ROWS * LTW;              // floats per staged channel
 };
 
 // Scheduling fences around each stage's MFMA group: needed while the kernels were register-starved
@@ -490,7 +483,7 @@ struct RingGeo {
 // consumer split its own schedule is as good or better (layers 4+5: 286 -> 265 us), except for the
 // 6-tile (Cout 8) push kernels, which keep them.
 constexpr int FENCE_MIN_NT = 6;
-template <int MODE, int K, int VAR = 0>
+template <int MODE, int K>
 struct MfmaGeom {
     static constexpr int CIN = MODE == 2 ? gin_of(K) : cin_of(K);
     static constexpr int COUT = cout_of(K);
@@ -500,8 +493,7 @@ struct MfmaGeom {
     // channels per staged chunk: 4, except 3 for the compute-bound layer 2 (21 input channels pad
     // to nothing instead of 24: -12 % MFMAs; measured 242 -> 229 us).  Layer 3 (27 = 9 x 3) is at
     // the HBM roof and got slower with the smaller chunks (more barriers, less data in flight)
-    // (VAR = 2, two workgroups per CU: layer 3's 27 channels in 3-channel chunks too, so that its two-stage ring fits 80 KB)
-    static constexpr int CH = (MODE != 2 && (CIN == 21 || (VAR == 2 && CIN == 27))) ? 3 : LCH;
+    static constexpr int CH = (MODE != 2 && CIN == 21) ? 3 : LCH;
     static constexpr int NCHUNK = (CIN + CH - 1) / CH;
     static constexpr int DMA = CH * P_ROWS;                        // row transfers per chunk
     static constexpr bool FENCE = FENCE_MIN_NT <= NT;             // scheduling fences around the MFMA groups
@@ -512,11 +504,6 @@ struct MfmaGeom {
 // no s_waitcnt vmcnt(0) in front of the consumers' ds_reads (with the builtin it does, which
 // serialises every prefetch with the compute it was meant to overlap).  Completion is tracked
 // by hand with s_waitcnt vmcnt(<row transfers per chunk>): "everything but the newest chunk has landed".
-__device__ __forceinline__ void dma_row16(unsigned long long src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
-
 __device__ __forceinline__ void dma_row4(unsigned long long src, unsigned lds_byte_addr) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off"
                  :: "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
@@ -540,14 +527,13 @@ struct RingArgs {
 // Only lanes left of the image's right edge are active (EXEC is restricted by the caller; the
 // consumers never read staged columns >= W).  Channels >= CIN and rows outside the image come
 // from the 1 KB of zero words behind the packed parameters.  All address arithmetic is scalar.
-template <int MODE, int K, int HALF = 0>
+template <int MODE, int K>
 __device__ __forceinline__ void ring_stage(const LayerArgs& a, unsigned slot_byte, int n, int ty0, int c,
                                            size_t HW, unsigned voff, const float* zero) {
-    constexpr int CIN = MfmaGeom<MODE, K, HALF>::CIN;
-    constexpr int PT_H = RingGeo<HALF>::ROWS, P_ROWS = RingGeo<HALF>::SROWS;       // (shadow the default geometry)
+    constexpr int CIN = MfmaGeom<MODE, K>::CIN;
     const unsigned long long zaddr = (unsigned long long)zero;
     const bool interior = ty0 >= 1 && ty0 + PT_H < a.H;                            // rows ty0-1 .. ty0+PT_H all inside
-    constexpr int CH = MfmaGeom<MODE, K, HALF>::CH;
+    constexpr int CH = MfmaGeom<MODE, K>::CH;
 #pragma unroll
     for (int cc = 0; cc < CH; ++cc) {
         const int ch = c * CH + cc;
@@ -590,11 +576,11 @@ __device__ __forceinline__ void ring_stage(const LayerArgs& a, unsigned slot_byt
 // consumer: one staged chunk = CH stages of 3 K-steps (dy) x 4 segments x NT row tiles.  The LDS
 // operands of stage cc+1 are requested before the MFMAs of stage cc (register double buffer);
 // sched_barriers keep the compiler from hoisting every load of the chunk to the top.
-template <int MODE, int K, int NT_, int HALF = 0>
-__device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[RingGeo<HALF>::SEGS][NT_], const float* buf, const float* wl,
+template <int MODE, int K, int NT_>
+__device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[M_SEGS][NT_], const float* buf, const float* wl,
                                            int c0, int boffq, int lane) {
-    using G = MfmaGeom<MODE, K, HALF>;
-    constexpr int M_SEGS = RingGeo<HALF>::SEGS, P_PLANE = RingGeo<HALF>::PLANE;    // (shadow the default geometry)
+    using G = MfmaGeom<MODE, K>;
+    constexpr int P_PLANE = RingGeo<0>::PLANE;
     float w[2][3][G::NTP], b[2][3][M_SEGS];
     auto load_stage = [&](int cc, int sel) {
 #pragma unroll
@@ -613,14 +599,10 @@ __device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[RingGeo<HALF>::SEGS][NT_
                     }
                 }
             }
-            // the lane's consecutive pixels: one 16-byte (8-byte) read feeds the four (two) "segments"
-            if constexpr (M_SEGS == 4) {
-                const float4 bq = *reinterpret_cast<const float4*>(buf + cc * P_PLANE + dy * LTW + boffq);
-                b[sel][dy][0] = bq.x; b[sel][dy][1] = bq.y; b[sel][dy][2] = bq.z; b[sel][dy][3] = bq.w;
-            } else {
-                const float2 bq = *reinterpret_cast<const float2*>(buf + cc * P_PLANE + dy * LTW + boffq);
-                b[sel][dy][0] = bq.x; b[sel][dy][1] = bq.y;
-            }
+            // the lane's consecutive pixels: one 16-byte read feeds the four "segments"
+            static_assert(M_SEGS == 4, "one float4 per lane");
+            const float4 bq = *reinterpret_cast<const float4*>(buf + cc * P_PLANE + dy * LTW + boffq);
+            b[sel][dy][0] = bq.x; b[sel][dy][1] = bq.y; b[sel][dy][2] = bq.z; b[sel][dy][3] = bq.w;
         }
     };
     load_stage(0, 0);
@@ -639,13 +621,11 @@ __device__ __forceinline__ void mfma_chunk(f32x4 (&acc)[RingGeo<HALF>::SEGS][NT_
     }
 }
 
-template <int MODE, int K, int HALF = 0>                  // HALF: the RingGeo variant (0 default, 1 half tiles, 2 two-stage ring)
+template <int MODE, int K, int HALF = 0>                  // HALF: the RingGeo variant (0 default, 2 two-stage ring; the name dates from variant 1)
 __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(RingArgs ra) {
-    using G = MfmaGeom<MODE, K, HALF>;
+    using G = MfmaGeom<MODE, K>;
     constexpr int CIN = G::CIN, COUT = G::COUT, NT = G::NT, NTP = G::NTP, NCHUNK = G::NCHUNK;
-    // (shadow the default geometry; the half-tile ring is sized by the layer's chunk so that two workgroups fit a CU)
-    constexpr int PT_H = RingGeo<HALF>::ROWS, M_SEGS = RingGeo<HALF>::SEGS;
-    constexpr int P_BUF = (HALF ? G::CH : LCH) * RingGeo<HALF>::PLANE;
+    constexpr int P_BUF = (HALF ? G::CH : LCH) * RingGeo<HALF>::PLANE;     // the two-stage ring is sized by the layer's chunk
     constexpr int RING = RingGeo<HALF>::STAGES, AHEAD = RING - 1;      // (shadow) chunks the producer runs ahead of the consumers
     __shared__ __attribute__((aligned(16))) float lds[RING * P_BUF + G::WL + P_CONS * 2 * 8];
     const LayerArgs& a = ra.a;
@@ -685,18 +665,18 @@ __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(
 #pragma unroll 1
         for (int pre = 0; pre < AHEAD && pre < nitems; ++pre) {
             const int tile = t_begin + (pre / NCHUNK) * t_step, n = tile / ra.tiles_y;
-            ring_stage<MODE, K, HALF>(a, lds0 + pre * (P_BUF * 4), n, (tile - n * ra.tiles_y) * PT_H, pre % NCHUNK, HW, voff, zero);
+            ring_stage<MODE, K>(a, lds0 + pre * (P_BUF * 4), n, (tile - n * ra.tiles_y) * PT_H, pre % NCHUNK, HW, voff, zero);
         }
         int tile = t_begin, c = 0, slot = 0;
 #pragma unroll 1
         for (int q = 0; q < nitems; ++q) {
             // chunk q has landed (only chunk q+1 may still be in flight); consumers are done with q-1
-            if (AHEAD == 2 && q + 1 < nitems && !(DMC_ABL(ra.ablate) & 1)) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(G::CH * RingGeo<HALF>::SROWS) : "memory");
+            if (AHEAD == 2 && q + 1 < nitems && !(DMC_ABL(ra.ablate) & 1)) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(G::CH * P_ROWS) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
             if (q + AHEAD < nitems && !(DMC_ABL(ra.ablate) & 1)) {
                 const int c2 = c + AHEAD, tile2 = tile + (c2 / NCHUNK) * t_step, n2 = tile2 / ra.tiles_y;
                 int slot2 = slot + AHEAD; slot2 = slot2 >= RING ? slot2 - RING : slot2;
-                ring_stage<MODE, K, HALF>(a, lds0 + (unsigned)slot2 * (P_BUF * 4), n2, (tile2 - n2 * ra.tiles_y) * PT_H,
+                ring_stage<MODE, K>(a, lds0 + (unsigned)slot2 * (P_BUF * 4), n2, (tile2 - n2 * ra.tiles_y) * PT_H,
                                     c2 % NCHUNK, HW, voff, zero);
             }
             slot = slot + 1 == RING ? 0 : slot + 1;
@@ -730,7 +710,7 @@ __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(
     for (int q = 0; q < nitems; ++q) {
         asm volatile("s_barrier" ::: "memory");
         if (!(DMC_ABL(ra.ablate) & 4) || r < 4)      // ablate 4: one computing wave per SIMD (waves 4 .. 6 only keep the barriers)
-            mfma_chunk<MODE, K, NT, HALF>(acc, lds + slot * P_BUF, wl, c * G::CH, boffq, lane);
+            mfma_chunk<MODE, K, NT>(acc, lds + slot * P_BUF, wl, c * G::CH, boffq, lane);
         slot = slot + 1 == RING ? 0 : slot + 1;
         if (++c < NCHUNK) continue;
         c = 0;
@@ -743,7 +723,6 @@ __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(
         const size_t pix = tile_pix + (inside ? p0 : 0);
         float4 extra[COUT];              // MODE 1: mv (delta add), MODE 2: y_K (LeakyReLU'): one batch of loads
         if (MODE != 0) {
-            static_assert(MODE == 0 || HALF != 1, "the half-tile variant is built for the forward's inner layers only");
 #pragma unroll
             for (int co = 0; co < COUT; ++co)
                 extra[co] = MODE == 1 ? (a.add_mv ? *reinterpret_cast<const float4*>(a.mv + ((size_t)n * 2 + co) * HW + pix)
@@ -793,10 +772,7 @@ __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(
                     v[e] *= ex[e] > 0.f ? 1.f : 0.1f;
                 }
             }
-            if constexpr (HALF == 1) {
-                if (inside && !(DMC_ABL(ra.ablate) & 2))
-                    *reinterpret_cast<float2*>(a.feat_out + ((size_t)n * NFEAT + (yoff(K) - NIN) + co) * HW + pix) = make_float2(v[0], v[1]);
-            } else if (inside && !(DMC_ABL(ra.ablate) & 2)) {
+            if (inside && !(DMC_ABL(ra.ablate) & 2)) {
                 const float4 o = make_float4(v[0], v[1], v[2], v[3]);
                 if (MODE == 0) *reinterpret_cast<float4*>(a.feat_out + ((size_t)n * NFEAT + (yoff(K) - NIN) + co) * HW + pix) = o;
                 else if (MODE == 1) *reinterpret_cast<float4*>(a.out + ((size_t)n * 2 + co) * HW + pix) = o;
@@ -851,7 +827,7 @@ __device__ __forceinline__ void wino_window(f32x2 (&d)[4][3], const float* p) {
 constexpr int WN_PAD = 4;                          // floats in front of the ring: column -1 of its first row
 template <int MODE, int K>
 struct WinoGeom {
-    using G = MfmaGeom<MODE, K, 0>;
+    using G = MfmaGeom<MODE, K>;
     static constexpr int CIN = G::CIN, COUT = G::COUT, CH = G::CH, NCHUNK = G::NCHUNK;
     static constexpr int NT = (COUT + 3) / 4;                     // row tiles = output channels / 4
     static constexpr int WL = NCHUNK * CH * NT * 64;              // [ci][t][position quad][row-in-tile][4], zero for ci >= CIN
@@ -862,7 +838,7 @@ template <int MODE, int K, int DBG = 0>     // DBG (measurement only, option gen
 __global__ __launch_bounds__(LTHREADS, 2) void gen_wino_kernel(RingArgs ra) {
     static_assert(MODE == 0 || MODE == 2, "hidden layers of the forward / data-gradient groups");
     using WG = WinoGeom<MODE, K>;
-    using G = MfmaGeom<MODE, K, 0>;
+    using G = MfmaGeom<MODE, K>;
     constexpr int CIN = WG::CIN, COUT = WG::COUT, NT = WG::NT, NCHUNK = WG::NCHUNK, CH = WG::CH;
     constexpr int P_BUF = LCH * RingGeo<0>::PLANE;
     constexpr int AHEAD = RING - 1;
@@ -924,7 +900,7 @@ __global__ __launch_bounds__(LTHREADS, 2) void gen_wino_kernel(RingArgs ra) {
 #pragma unroll 1
         for (int pre = 0; pre < AHEAD && pre < nitems; ++pre) {
             const int tile = t_begin + (pre / NCHUNK) * t_step, n = tile / ra.tiles_y;
-            ring_stage<MODE, K, 0>(a, lds0 + pre * (P_BUF * 4), n, (tile - n * ra.tiles_y) * PT_H, pre % NCHUNK, HW, voff, zero);
+            ring_stage<MODE, K>(a, lds0 + pre * (P_BUF * 4), n, (tile - n * ra.tiles_y) * PT_H, pre % NCHUNK, HW, voff, zero);
         }
         int tile = t_begin, c = 0, slot = 0;
 #pragma unroll 1
@@ -934,7 +910,7 @@ __global__ __launch_bounds__(LTHREADS, 2) void gen_wino_kernel(RingArgs ra) {
             if (q + AHEAD < nitems && !(DMC_ABL(ra.ablate) & 1)) {
                 const int c2 = c + AHEAD, tile2 = tile + (c2 / NCHUNK) * t_step, n2 = tile2 / ra.tiles_y;
                 int slot2 = slot + AHEAD; slot2 = slot2 >= RING ? slot2 - RING : slot2;
-                ring_stage<MODE, K, 0>(a, lds0 + (unsigned)slot2 * (P_BUF * 4), n2, (tile2 - n2 * ra.tiles_y) * PT_H,
+                ring_stage<MODE, K>(a, lds0 + (unsigned)slot2 * (P_BUF * 4), n2, (tile2 - n2 * ra.tiles_y) * PT_H,
                                        c2 % NCHUNK, HW, voff, zero);
             }
             slot = slot + 1 == RING ? 0 : slot + 1;
@@ -1723,37 +1699,6 @@ struct WgradArgs {
 // floats of the tile image; every lane supplies its own source address (or the address of a zero
 // word for pixels outside the image and for padding), so the padded / halo'd layout costs nothing
 // and no VGPRs are tied up by data in flight.
-// LDS-DMA of one tile (W % 4 == 0): one dwordx4 instruction moves half a plane (5 rows x 10
-// chunks = 50 lanes x 16 B), so the plane base is wave-uniform and a lane only contributes its
-// fixed (row, chunk): 66 instructions per tile, ~8 per wave, ~10 vector integer ops each.
-// (Issue cost matters: ~100 cycles per LDS-DMA instruction, and decoding a flat 64-float chunk per
-// lane cost ~25 vector ops each and held the MFMA rate at 70 % -- tools/ubench/mfma_f32_issue.hip.)
-__device__ __forceinline__ void wgrad_dma_tile(const WgradArgs& a, float* buf, int tile,
-                                               int per_frame, size_t HW, int pw, int lane,
-                                               const float* zero) {
-    const int n = tile / per_frame, r0 = tile - n * per_frame;
-    const int ty0 = (r0 / a.tiles_x) * WT_H, tx0 = (r0 % a.tiles_x) * WT_W;
-    const float* mvp = a.mv + (size_t)n * 2 * HW;
-    const float* rsp = a.res + (size_t)n * 3 * HW;
-    const float* ftp = a.feat + (size_t)n * NFEAT * HW;
-    const int lrow = lane / 10, chunk = lane - lrow * 10;      // lanes 0..49
-    const int xx = tx0 - 4 + 4 * chunk;
-    const bool colok = xx >= 0 && xx < a.W;
-    if (lane < 50) {
-#pragma unroll 1
-        for (int hp = pw; hp < 66; hp += 8) {                   // half-planes, wave-uniform
-            const int plane = hp >> 1, row = (hp & 1) * 5 + lrow;
-            const int yy = ty0 - 1 + row;
-            const float* base = plane < 2 ? mvp + (size_t)plane * HW
-                              : plane < NIN ? rsp + (size_t)(plane - 2) * HW
-                                            : ftp + (size_t)(plane - NIN) * HW;
-            const float* src = (colok && yy >= 0 && yy < a.H) ? base + (size_t)yy * a.W + xx : zero;
-            dma_row16((unsigned long long)src,
-                      (unsigned)(size_t)(lptr_t)(buf + plane * WX_PLANE + (hp & 1) * 5 * WX_PITCH));
-        }
-    }
-}
-
 // Any W: dword granularity, one instruction per (plane, row), 34 lanes.
 __device__ __forceinline__ void wgrad_dma_tile_generic(const WgradArgs& a, float* buf, int tile,
                                                        int per_frame, size_t HW, int pw, int lane,
@@ -1779,7 +1724,7 @@ __device__ __forceinline__ void wgrad_dma_tile_generic(const WgradArgs& a, float
 // issues its share of the LDS-DMA for the NEXT tile (asynchronous, no VGPRs), then runs the MFMAs
 // of one row (8 groups of 4 pixels) of the CURRENT tile; two MFMA waves per SIMD cover each
 // other's LDS gathers (one wave per SIMD measured 50 % matrix-pipe utilisation).
-template <bool VEC4>
+template <bool VEC4>          // false only: W % 4 == 0 takes gen_bwd_weight_pc_kernel (the 16-byte form of this kernel is removed)
 __global__ __launch_bounds__(512, 2) void gen_bwd_weight_kernel(WgradArgs a, const float* zero) {
     __shared__ __attribute__((aligned(16))) float lds2[2 * WT_LDS];
     const int lane = threadIdx.x & 63;
@@ -1831,8 +1776,7 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_kernel(WgradArgs a, con
     };
     int it = 0;
     if ((int)blockIdx.x < ntiles) {
-        if (VEC4) wgrad_dma_tile(a, lds2, blockIdx.x, per_frame, HW, wave, lane, zero);
-        else wgrad_dma_tile_generic(a, lds2, blockIdx.x, per_frame, HW, wave, lane, zero);
+        wgrad_dma_tile_generic(a, lds2, blockIdx.x, per_frame, HW, wave, lane, zero);
         request_row(blockIdx.x, cur0, cur1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the inline-asm LDS-DMA is invisible to the compiler
@@ -1841,8 +1785,7 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_kernel(WgradArgs a, con
         const float* lds = lds2 + (it & 1) * WT_LDS;
         const bool more = tile + (int)gridDim.x < ntiles;
         if (more) {
-            if (VEC4) wgrad_dma_tile(a, lds2 + ((it + 1) & 1) * WT_LDS, tile + gridDim.x, per_frame, HW, wave, lane, zero);
-            else wgrad_dma_tile_generic(a, lds2 + ((it + 1) & 1) * WT_LDS, tile + gridDim.x, per_frame, HW, wave, lane, zero);
+            wgrad_dma_tile_generic(a, lds2 + ((it + 1) & 1) * WT_LDS, tile + gridDim.x, per_frame, HW, wave, lane, zero);
             request_row(tile + gridDim.x, nxt0, nxt1);
         }
         const int r0 = tile % per_frame;
@@ -2011,23 +1954,21 @@ __device__ __forceinline__ f32x4 gen_mfma_x3(const GenSplit3& a, const GenSplit3
     return c;
 }
 
-// X3 = true: the same GEMM in bf16x3 arithmetic -- one v_mfma_f32_16x16x32_bf16 k-block = the 32 pixels of a tile row
-// (lane (j, kq) holds pixels 8 kq .. 8 kq + 7 of its gradient plane / its (ci, tap) column: eight consecutive floats of an
-// LDS row), six MFMAs of 16 cycles per accumulator tile and row where the fp32 form issues eight of 32: 2.67x fewer
-// matrix cycles; the split of a fragment (44 VALU instructions) is shared by the two row tiles.  Same C layout, same
-// reductions.
-// X3 = 2: the bf16x3 form with the three horizontal taps of a (ci, dy) pair in ONE lane: column tile tt = 3 gt + dx holds
-// columns g = 16 gt + j = 3 ci + dy; the lane reads the 10 floats x[8 kq - 1 .. 8 kq + 8] of its row once, splits them once
-// (40 VALU instructions) and forms the three 8-pixel fragments from shared packed pairs (dx = 0: P0..P3, dx = 2: P1..P4,
-// dx = 1: Q0..Q3) -- 67 VALU instructions per three column tiles where X3 = 1 spends 132.  7 x 3 = 21 column tiles for
-// the rows of layers 2-5 (+ the ones column for their bias at g = 99, dx = 0), 3 x 3 for those of layers 0 / 1.
-template <int X3>
+// The GEMM runs in bf16x3 arithmetic -- one v_mfma_f32_16x16x32_bf16 k-block = the 32 pixels of a tile row (lane (j, kq)
+// holds pixels 8 kq .. 8 kq + 7 of its gradient plane: eight consecutive floats of an LDS row), six MFMAs of 16 cycles per
+// accumulator tile and row where an fp32 form issues eight of 32: 2.67x fewer matrix cycles; the split of an A fragment
+// (44 VALU instructions) is shared by the two row tiles.
+// The three horizontal taps of a (ci, dy) pair sit in ONE lane: column tile tt = 3 gt + dx holds columns g = 16 gt + j =
+// 3 ci + dy; the lane reads the 10 floats x[8 kq - 1 .. 8 kq + 8] of its row once, splits them once (40 VALU instructions)
+// and forms the three 8-pixel fragments from shared packed pairs (dx = 0: P0..P3, dx = 2: P1..P4, dx = 1: Q0..Q3) -- 67
+// VALU instructions per three column tiles where a split per (ci, tap) column spent 132.  7 x 3 = 21 column tiles for the
+// rows of layers 2-5 (+ the ones column for their bias at g = 99, dx = 0), 3 x 3 for those of layers 0 / 1.
+// (The fp32 form and the two earlier bf16x3 forms of this kernel, gen_wgrad_path 1 .. 3, are removed: DESIGN 4, kernel table.)
 __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) {
     __shared__ __attribute__((aligned(16))) float lds2[2 * PW_BUF];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int j = lane & 15, kq = lane >> 4;          // column / pixel-in-group of this lane
-    const bool ones = (16 * 18 + j) == BIAS_COL;      // bias column lives in N tile 18
     const size_t HW = (size_t)a.H * a.W;
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds2;
     const int per_frame = a.tiles_x * a.tiles_y;
@@ -2042,7 +1983,7 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
         return xcd_sched ? (i * 8 + (int)(blockIdx.x & 7)) * xs_per + (int)(blockIdx.x >> 3) : (int)blockIdx.x + i * (int)gridDim.x;
     };
 
-    constexpr int NA = X3 >= 2 ? NT3_A : NT_A, NB = X3 >= 2 ? NT3_B : NT_B, WP = (NA + NB) * 256;
+    constexpr int NA = NT3_A, NB = NT3_B, WP = (NA + NB) * 256;
     f32x4 accA[NA], accB[NB];
 #pragma unroll
     for (int t = 0; t < NA; ++t) accA[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -2057,11 +1998,13 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
             const int next = tile_of(it + 1);
             if (next < ntiles)
                 wgrad_stage(a, lds2 + ((it + 1) & 1) * PW_BUF, lds0 + (unsigned)(((it + 1) & 1) * PW_BUF) * 4, next, per_frame, HW, lane,
-                            true, 0, X3 != 0 ? 0 : 30);
+                            true, 0, 0);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
     } else {
-        // per-lane gather offsets of the B fragments (x[(ci,tap)][pixel kq of the group])
+        // (offB: the gather offsets of the removed per-(ci, tap) forms.  Nothing reads them and no instruction computes them, but
+        // without these lines the compiler schedules this kernel's prologue differently; the removal of the variants was held to
+        // unchanged assembly, so they go with the next change to this kernel's code)
         int offB[NT_B];
 #pragma unroll
         for (int t = 0; t < NT_B; ++t) {
@@ -2070,14 +2013,15 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
             const int ci = nn / 9, tap = nn - ci * 9;
             offB[t] = ci * PW_XPLANE + (tap / 3) * WX_PITCH + (tap % 3) + kq + WX_COL0;
         }
-        int offW[7];                                       // X3 == 2: start of this lane's 10-float window per group tile
+        (void)offB;
+        int offW[7];                                       // start of this lane's 10-float window per group tile
 #pragma unroll
         for (int gt = 0; gt < 7; ++gt) {
             int g = 16 * gt + j;
             g = g < 99 ? g : 98;
             offW[gt] = (g / 3) * PW_XPLANE + (g % 3) * WX_PITCH + WX_COL0 + 8 * kq;
         }
-        const bool ones3 = j == 3;                         // X3 == 2: g = 99 (group tile 6, column 3) is the ones column
+        const bool ones3 = j == 3;                         // g = 99 (group tile 6, column 3) is the ones column
         // A fragments: row j of M tile A = gradient plane j; of M tile B = plane 16 + j (j < 14), else zero
         const bool rowB = j < 14;
         const int offA0 = PW_X + j * PW_GPLANE + kq;
@@ -2090,116 +2034,75 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
         asm volatile("s_barrier" ::: "memory");
         for (int tile = tile_of(0); tile < ntiles; tile = tile_of(++it)) {
             const float* lds = lds2 + (it & 1) * PW_BUF;
-            if constexpr (X3 != 0) {
-                const int next = tile_of(it + 1);
-                if (next < ntiles)                        // this wave's share of the next tile's gradient planes
-                    wgrad_stage(a, lds2 + ((it + 1) & 1) * PW_BUF, lds0 + (unsigned)(((it + 1) & 1) * PW_BUF) * 4, next, per_frame, HW, lane,
-                                false, (30 * wave) / PW_H, (30 * (wave + 1)) / PW_H);
-                // fragments: 8 consecutive pixels 8 kq .. 8 kq + 7 of this wave's tile row (offA / offB carry + kq: + 7 kq more)
-                const int sA = wave * WT_W + 7 * kq, sB = wave * WX_PITCH + 7 * kq;
-                float av[8];
-                const float4 p0 = *reinterpret_cast<const float4*>(lds + offA0 + sA), p1 = *reinterpret_cast<const float4*>(lds + offA0 + sA + 4);
-                av[0] = p0.x; av[1] = p0.y; av[2] = p0.z; av[3] = p0.w; av[4] = p1.x; av[5] = p1.y; av[6] = p1.z; av[7] = p1.w;
+            const int next = tile_of(it + 1);
+            if (next < ntiles)                        // this wave's share of the next tile's gradient planes
+                wgrad_stage(a, lds2 + ((it + 1) & 1) * PW_BUF, lds0 + (unsigned)(((it + 1) & 1) * PW_BUF) * 4, next, per_frame, HW, lane,
+                            false, (30 * wave) / PW_H, (30 * (wave + 1)) / PW_H);
+            // fragments: 8 consecutive pixels 8 kq .. 8 kq + 7 of this wave's tile row (offA carries + kq: + 7 kq more)
+            const int sA = wave * WT_W + 7 * kq;
+            float av[8];
+            const float4 p0 = *reinterpret_cast<const float4*>(lds + offA0 + sA), p1 = *reinterpret_cast<const float4*>(lds + offA0 + sA + 4);
+            av[0] = p0.x; av[1] = p0.y; av[2] = p0.z; av[3] = p0.w; av[4] = p1.x; av[5] = p1.y; av[6] = p1.z; av[7] = p1.w;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) bias_a += av[e];
-                const GenSplit3 a0s = gen_split_bf16x3(av);
-                const float4 q0 = *reinterpret_cast<const float4*>(lds + offA1 + sA), q1 = *reinterpret_cast<const float4*>(lds + offA1 + sA + 4);
-                av[0] = q0.x; av[1] = q0.y; av[2] = q0.z; av[3] = q0.w; av[4] = q1.x; av[5] = q1.y; av[6] = q1.z; av[7] = q1.w;
+            for (int e = 0; e < 8; ++e) bias_a += av[e];
+            const GenSplit3 a0s = gen_split_bf16x3(av);
+            const float4 q0 = *reinterpret_cast<const float4*>(lds + offA1 + sA), q1 = *reinterpret_cast<const float4*>(lds + offA1 + sA + 4);
+            av[0] = q0.x; av[1] = q0.y; av[2] = q0.z; av[3] = q0.w; av[4] = q1.x; av[5] = q1.y; av[6] = q1.z; av[7] = q1.w;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) av[e] = rowB ? av[e] : 0.f;
-                const GenSplit3 a1s = gen_split_bf16x3(av);
-                if constexpr (X3 >= 2) {
+            for (int e = 0; e < 8; ++e) av[e] = rowB ? av[e] : 0.f;
+            const GenSplit3 a1s = gen_split_bf16x3(av);
 #pragma unroll
-                    for (int gt = 0; gt < 7; ++gt) {
-                        float wv[10];
-                        if constexpr (X3 == 3) {
-                            // the window starts at float 3 (mod 4) of its row: one 8-byte, two 16-byte, one 8-byte read.  Every
-                            // lane's address is the same mod 4 floats (rows and planes are 16-byte multiples for the LDS-DMA),
-                            // so dword reads find 8 of the 32 banks (4-way conflicts in each half-wave); the wide reads are
-                            // serviced in 16-byte slots of the 256-byte bank row: modelled 180 LDS cycles per wave and tile
-                            // where the dword reads take 640
-                            const float* wp = lds + offW[gt] + wave * WX_PITCH;
-                            typedef float f32x2 __attribute__((ext_vector_type(2)));
-                            const f32x2 e0 = *static_cast<const f32x2*>(__builtin_assume_aligned(wp - 1, 8));
-                            const f32x4 m0 = *static_cast<const f32x4*>(__builtin_assume_aligned(wp + 1, 16));
-                            const f32x4 m1 = *static_cast<const f32x4*>(__builtin_assume_aligned(wp + 5, 16));
-                            const f32x2 e9 = *static_cast<const f32x2*>(__builtin_assume_aligned(wp + 9, 8));
-                            wv[0] = e0.y; wv[1] = m0.x; wv[2] = m0.y; wv[3] = m0.z; wv[4] = m0.w;
-                            wv[5] = m1.x; wv[6] = m1.y; wv[7] = m1.z; wv[8] = m1.w; wv[9] = e9.x;
-                        } else {
+            for (int gt = 0; gt < 7; ++gt) {
+                float wv[10];
+                // the window starts at float 3 (mod 4) of its row: one 8-byte, two 16-byte, one 8-byte read.  Every
+                // lane's address is the same mod 4 floats (rows and planes are 16-byte multiples for the LDS-DMA),
+                // so dword reads find 8 of the 32 banks (4-way conflicts in each half-wave); the wide reads are
+                // serviced in 16-byte slots of the 256-byte bank row: modelled 180 LDS cycles per wave and tile
+                // where the dword reads take 640
+                const float* wp = lds + offW[gt] + wave * WX_PITCH;
+                typedef float f32x2 __attribute__((ext_vector_type(2)));
+                const f32x2 e0 = *static_cast<const f32x2*>(__builtin_assume_aligned(wp - 1, 8));
+                const f32x4 m0 = *static_cast<const f32x4*>(__builtin_assume_aligned(wp + 1, 16));
+                const f32x4 m1 = *static_cast<const f32x4*>(__builtin_assume_aligned(wp + 5, 16));
+                const f32x2 e9 = *static_cast<const f32x2*>(__builtin_assume_aligned(wp + 9, 8));
+                wv[0] = e0.y; wv[1] = m0.x; wv[2] = m0.y; wv[3] = m0.z; wv[4] = m0.w;
+                wv[5] = m1.x; wv[6] = m1.y; wv[7] = m1.z; wv[8] = m1.w; wv[9] = e9.x;
+                if (gt == 6 && ones3) {
 #pragma unroll
-                            for (int e = 0; e < 10; ++e) wv[e] = lds[offW[gt] + wave * WX_PITCH + e];
-                        }
-                        if (gt == 6 && ones3) {
-#pragma unroll
-                            for (int e = 0; e < 10; ++e) wv[e] = 1.f;
-                        }
-                        unsigned u[3][10];
-#pragma unroll
-                        for (int e = 0; e < 10; ++e) {
-                            u[0][e] = __float_as_uint(wv[e]);
-                            const float r1 = wv[e] - __uint_as_float(u[0][e] & 0xffff0000u);
-                            u[1][e] = __float_as_uint(r1);
-                            u[2][e] = __float_as_uint(r1 - __uint_as_float(u[1][e] & 0xffff0000u));
-                        }
-                        unsigned P[3][5], Q[3][4];
-#pragma unroll
-                        for (int sl = 0; sl < 3; ++sl) {
-#pragma unroll
-                            for (int k = 0; k < 5; ++k) P[sl][k] = __builtin_amdgcn_perm(u[sl][2 * k + 1], u[sl][2 * k], 0x07060302u);
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) Q[sl][k] = __builtin_amdgcn_perm(u[sl][2 * k + 2], u[sl][2 * k + 1], 0x07060302u);
-                        }
-#pragma unroll
-                        for (int dxi = 0; dxi < 3; ++dxi) {
-                            GenSplit3 bs;
-#pragma unroll
-                            for (int sl = 0; sl < 3; ++sl)
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) bs.s[sl][k] = dxi == 0 ? P[sl][k] : dxi == 2 ? P[sl][k + 1] : Q[sl][k];
-                            const int tt = 3 * gt + dxi;
-                            if (gt < 3) accA[tt < NA ? tt : 0] = gen_mfma_x3(a0s, bs, accA[tt < NA ? tt : 0]);
-                            accB[tt] = gen_mfma_x3(a1s, bs, accB[tt]);
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < NT_B; ++t) {
-                        float bv[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) bv[e] = lds[offB[t] + sB + e];
-                        if (t == 18 && ones) {
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) bv[e] = 1.f;
-                        }
-                        const GenSplit3 bs = gen_split_bf16x3(bv);
-                        if (t < 8) accA[t] = gen_mfma_x3(a0s, bs, accA[t]);
-                        accB[t < NB ? t : 0] = gen_mfma_x3(a1s, bs, accB[t < NB ? t : 0]);
-                    }
+                    for (int e = 0; e < 10; ++e) wv[e] = 1.f;
                 }
-            } else
+                unsigned u[3][10];
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const int sA = wave * WT_W + g * 4, sB = wave * WX_PITCH + g * 4;
-                const float a0 = lds[offA0 + sA];
-                const float a1r = lds[offA1 + sA];
-                const float a1 = rowB ? a1r : 0.f;
-                float b[NT_B];
+                for (int e = 0; e < 10; ++e) {
+                    u[0][e] = __float_as_uint(wv[e]);
+                    const float r1 = wv[e] - __uint_as_float(u[0][e] & 0xffff0000u);
+                    u[1][e] = __float_as_uint(r1);
+                    u[2][e] = __float_as_uint(r1 - __uint_as_float(u[1][e] & 0xffff0000u));
+                }
+                unsigned P[3][5], Q[3][4];
 #pragma unroll
-                for (int t = 0; t < NT_B; ++t) b[t] = lds[offB[t] + sB];
-                if (ones) b[18] = 1.f;
-                bias_a += a0;
+                for (int sl = 0; sl < 3; ++sl) {
 #pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    accA[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[t], accA[t], 0, 0, 0);
+                    for (int k = 0; k < 5; ++k) P[sl][k] = __builtin_amdgcn_perm(u[sl][2 * k + 1], u[sl][2 * k], 0x07060302u);
 #pragma unroll
-                for (int t = 0; t < NT_B; ++t)
-                    accB[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[t], accB[t], 0, 0, 0);
+                    for (int k = 0; k < 4; ++k) Q[sl][k] = __builtin_amdgcn_perm(u[sl][2 * k + 2], u[sl][2 * k + 1], 0x07060302u);
+                }
+#pragma unroll
+                for (int dxi = 0; dxi < 3; ++dxi) {
+                    GenSplit3 bs;
+#pragma unroll
+                    for (int sl = 0; sl < 3; ++sl)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) bs.s[sl][k] = dxi == 0 ? P[sl][k] : dxi == 2 ? P[sl][k + 1] : Q[sl][k];
+                    const int tt = 3 * gt + dxi;
+                    if (gt < 3) accA[tt < NA ? tt : 0] = gen_mfma_x3(a0s, bs, accA[tt < NA ? tt : 0]);
+                    accB[tt] = gen_mfma_x3(a1s, bs, accB[tt]);
+                }
             }
-            if constexpr (X3 != 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's transfers have landed
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this wave's transfers have landed
             asm volatile("s_barrier" ::: "memory");        // next tile staged, this buffer may be refilled
         }
-        // fold the row sums into accumulator slot 8 (N tile 18), column BIAS_COL - 288 = 9, in the MFMA
+        // fold the row sums into accumulator slot 9, column 3 (the ones column), in the MFMA
         // C layout: lane (j, kq) holds rows kq*4 + q of column j
         float tot = bias_a;
         tot += __shfl_xor(tot, 16);
@@ -2207,8 +2110,7 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float rv = __shfl(tot, kq * 4 + q);                  // lanes 0..15 hold rows 0..15
-            if constexpr (X3 >= 2) accA[9][q] = ones3 ? rv : 0.f;      // slot 9, column 3
-            else accA[8][q] = ones ? rv : 0.f;
+            accA[9][q] = ones3 ? rv : 0.f;                             // slot 9, column 3
         }
     }
     // cross-wave reduction in LDS, fixed order (wave 0 stores, waves 1..6 add in turn)
@@ -2370,7 +2272,7 @@ int launch_layer(LayerArgs a, int n0, int N, hipStream_t s) {
     // Cout-6 layers lose (18 instead of 15 MFMAs per channel and pixel), the rest are at the HBM roof
     constexpr bool GATHER_FORM = (MODE == 0 && K <= 1) || (MODE == 2 && K == 1);
     const int gpath = option(OPT_GEN_GATHER);
-    if (GATHER_FORM && gpath == 1 && (path == 1 || path == 3 || path == 4 || path == 5) && a.W % 4 == 0 && a.W <= P_MAXW) {
+    if (GATHER_FORM && gpath == 1 && path == 1 && a.W % 4 == 0 && a.W <= P_MAXW) {
         RingArgs ra;
         ra.ablate = 0;
         ra.a = a;
@@ -2378,12 +2280,11 @@ int launch_layer(LayerArgs a, int n0, int N, hipStream_t s) {
         ra.ntiles = ra.tiles_y * N;
         const int wgs = ra.ntiles < num_cus() ? ra.ntiles : num_cus();
         if constexpr (GATHER_FORM) gen_layer_gather_kernel<MODE, K><<<wgs, G_THREADS, 0, s>>>(ra);
-    } else if (MODE == 0 && ((path == 1 && K == 2) || (MEASURE_BUILD && path == 4 && (K == 2 || K == 3))) && a.W % 4 == 0 && a.W <= P_MAXW) {
-        // variant (iii): the default tile with a two-stage ring, two 8-wave workgroups per CU.  Forward layer 2 (the most
-        // matrix-bound layer) gains 7.5 % from the second resident workgroup (214.7 -> 198.5 us, matrix pipe busy 0.534 ->
-        // 0.573) and takes it by default; layer 3 (HBM-bound, needs 3-channel chunks to fit) loses 1.7 %: option value 4 only.
-        // Option value 5 = every layer on the three-stage single-workgroup kernel (the default before)
-        if constexpr (MODE == 0 && (K == 2 || (MEASURE_BUILD && K == 3))) {
+    } else if (MODE == 0 && K == 2 && path == 1 && a.W % 4 == 0 && a.W <= P_MAXW) {
+        // the default tile with a two-stage ring, two 8-wave workgroups per CU.  Forward layer 2 (the most matrix-bound
+        // layer) gains 7.5 % from the second resident workgroup (214.7 -> 198.5 us, matrix pipe busy 0.534 -> 0.573);
+        // layer 3 (HBM-bound, needs 3-channel chunks to fit) lost 1.7 % and stays on the three-stage kernel (profiles/r3_gen_variant_ii.txt)
+        if constexpr (MODE == 0 && K == 2) {
             RingArgs ra;
             ra.a = a;
             ra.tiles_y = (a.H + PT_H - 1) / PT_H;
@@ -2392,26 +2293,17 @@ int launch_layer(LayerArgs a, int n0, int N, hipStream_t s) {
             const int wgs = ra.ntiles < 2 * num_cus() ? ra.ntiles : 2 * num_cus();
             gen_layer_mfma_kernel<MODE, K, 2><<<wgs, LTHREADS, 0, s>>>(ra);
         }
-    } else if (MEASURE_BUILD && path == 3 && MODE == 0 && (K == 2 || K == 3) && a.W % 4 == 0 && a.W <= P_MAXW) {
-        // measurement variant (round-2 verdict, variant ii): 4-row tiles, two 8-wave workgroups per CU -- -DDMC_MEASURE build only
-        if constexpr (MEASURE_BUILD && MODE == 0 && (K == 2 || K == 3)) {
+    } else if (path == 1 && a.W % 4 == 0 && a.W <= P_MAXW) {
+        if constexpr (!(MODE == 0 && K == 2)) {       // (forward layer 2 took the two-stage branch above)
             RingArgs ra;
+            ra.ablate = 0;
             ra.a = a;
-            ra.tiles_y = (a.H + RingGeo<1>::ROWS - 1) / RingGeo<1>::ROWS;
+            ra.tiles_y = (a.H + PT_H - 1) / PT_H;
             ra.ntiles = ra.tiles_y * N;
             ra.ablate = option(OPT_GEN_ABLATE);
-            const int wgs = ra.ntiles < 2 * num_cus() ? ra.ntiles : 2 * num_cus();
-            gen_layer_mfma_kernel<MODE, K, 1><<<wgs, LTHREADS, 0, s>>>(ra);
+            const int wgs = ra.ntiles < num_cus() ? ra.ntiles : num_cus();
+            gen_layer_mfma_kernel<MODE, K><<<wgs, LTHREADS, 0, s>>>(ra);
         }
-    } else if ((path == 1 || path == 3 || path == 4 || path == 5) && a.W % 4 == 0 && a.W <= P_MAXW) {
-        RingArgs ra;
-        ra.ablate = 0;
-        ra.a = a;
-        ra.tiles_y = (a.H + PT_H - 1) / PT_H;
-        ra.ntiles = ra.tiles_y * N;
-        ra.ablate = option(OPT_GEN_ABLATE);
-        const int wgs = ra.ntiles < num_cus() ? ra.ntiles : num_cus();
-        gen_layer_mfma_kernel<MODE, K><<<wgs, LTHREADS, 0, s>>>(ra);
     }
     else if (DMA_WINS && a.W % 4 == 0 && a.W <= LTW) gen_layer_dma_kernel<MODE, K><<<grid, LTHREADS, 0, s>>>(a);
     else if (a.W % 4 == 0) gen_layer_kernel<MODE, K, true><<<grid, LTHREADS, 0, s>>>(a);
@@ -2500,7 +2392,7 @@ static int gen_tiny_fwd_impl(const float* mv, const float* res, const float* con
         if ((rc = ((x3mask >> 2) & 1) ? x3(2) : launch_layer<0, 2>(a, n0, nn, s))) return rc;
         if ((rc = launch_layer<0, 3>(a, n0, nn, s))) return rc;
         const int fuse45 = option(OPT_GEN_FUSE45), lpath = option(OPT_GEN_LAYER_PATH);
-        if (fuse45 && (lpath == 1 || lpath == 3 || lpath == 4 || lpath == 5) && W % 4 == 0 && W <= P_MAXW) {
+        if (fuse45 && lpath == 1 && W % 4 == 0 && W <= P_MAXW) {
             RingArgs ra;
             ra.ablate = 0;
             ra.a = a;
@@ -2593,15 +2485,7 @@ int dmc_gen_tiny_bwd(const float* mv, const float* res, const float* const* w, c
     la.pk = workspace; la.out = nullptr; la.H = H; la.W = W; la.add_mv = 0;
     la.mse_flow = nullptr; la.mse_part = nullptr;
     const int step = frames_per_pass(N, H, W);
-    // option gen_fused bit 1: the five data-gradient groups as ONE launch (gen_fused_bwd.hip) -- measured slower than the five
-    // launches (0.75 vs 0.60 ms): the kernel and the option value exist in the -DDMC_MEASURE build only
-#ifdef DMC_MEASURE
-    const bool fused_data = (option(OPT_GEN_FUSED) & 2) && gen_fused_supported(H, W);
-    if (fused_data && (rc = gen_fused_bwd_data(grad_out, saved, gbuf, workspace, N, H, W, s))) return rc;
-#else
-    const bool fused_data = false;
-#endif
-    for (int n0 = 0; n0 < N && !fused_data; n0 += step) {
+    for (int n0 = 0; n0 < N; n0 += step) {
         const int nn = (N - n0) < step ? (N - n0) : step;
         if ((rc = launch_layer<2, 4>(la, n0, nn, s))) return rc;
         if ((rc = launch_layer<2, 3>(la, n0, nn, s))) return rc;
@@ -2617,30 +2501,16 @@ int dmc_gen_tiny_bwd(const float* mv, const float* res, const float* const* w, c
     int groups = wgrad_groups(N, H, W);
     const int wpath = option(OPT_GEN_WGRAD_PATH);
     const bool rs = wpath == 5 && gen_wgrad_rs_supported(H, W);            // row-sliding kernel (gen_wgrad.hip)
-    const int layout3 = rs ? 2 : (W % 4 == 0 && wpath >= 3) ? 1 : 0;
+    const int layout3 = rs ? 2 : W % 4 == 0 ? 1 : 0;                       // the partials' layout (gen_bwd_weight_reduce_kernel)
     if (rs) {
         groups = gen_wgrad_rs_groups(N, H, W, groups);
         if ((rc = gen_wgrad_rs(mv, res, saved, grad_out, gbuf, workspace + PACKED_TOTAL, partials, N, H, W, groups, s))) return rc;
-    } else if (W % 4 == 0 && wpath >= 1) {
+    } else if (W % 4 == 0) {
         a.tiles_y = (H + PW_H - 1) / PW_H;
-        // paths 1 .. 3 (fp32 producer / consumer, earlier bf16x3 forms): slower predecessors of path 4, -DDMC_MEASURE build only
-        if (!MEASURE_BUILD || wpath >= 4) gen_bwd_weight_pc_kernel<3><<<groups, 512, 0, s>>>(a);
-        else if constexpr (MEASURE_BUILD) {
-            if (wpath == 3) gen_bwd_weight_pc_kernel<2><<<groups, 512, 0, s>>>(a);
-            else if (wpath == 2) gen_bwd_weight_pc_kernel<1><<<groups, 512, 0, s>>>(a);
-            else gen_bwd_weight_pc_kernel<0><<<groups, 512, 0, s>>>(a);
-        }
+        gen_bwd_weight_pc_kernel<<<groups, 512, 0, s>>>(a);
     } else {
         a.tiles_y = (H + WT_H - 1) / WT_H;
-        // (W % 4 == 0 reaches this branch only with gen_wgrad_path 0, a -DDMC_MEASURE value)
-        bool done = false;
-        if constexpr (MEASURE_BUILD) {
-            if (W % 4 == 0) {
-                gen_bwd_weight_kernel<true><<<groups, 512, 0, s>>>(a, workspace + PACKED_TOTAL);
-                done = true;
-            }
-        }
-        if (!done) gen_bwd_weight_kernel<false><<<groups, 512, 0, s>>>(a, workspace + PACKED_TOTAL);
+        gen_bwd_weight_kernel<false><<<groups, 512, 0, s>>>(a, workspace + PACKED_TOTAL);
     }
     if ((rc = check_launch("gen_bwd_weight"))) return rc;
     const int wpart = layout3 ? WPART3 : WPART;

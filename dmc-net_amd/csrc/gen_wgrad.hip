@@ -1,9 +1,9 @@
 // Weight gradient of EstimatorDenseNetTiny, row-sliding form (autograd of /root/reference/code/dmcnet/model.py:187-194; the GEMM
-// and its bf16x3 arithmetic are those of gen_bwd_weight_pc_kernel<3> in gen_tiny.hip):
+// and its bf16x3 arithmetic are those of gen_bwd_weight_pc_kernel in gen_tiny.hip):
 //
 //   dW[(k, co)][(ci, dy, dx)] = sum over pixels of g_k[co][y][x] * in[ci][y + dy - 1][x + dx - 1]
 //
-// gen_bwd_weight_pc_kernel<3> splits every fp32 operand into its three bf16 slices IN the consumer waves: the window of a (ci, dy)
+// gen_bwd_weight_pc_kernel splits every fp32 operand into its three bf16 slices IN the consumer waves: the window of a (ci, dy)
 // column is split by the three tile rows that use it, 4.8 vector instructions per MFMA next to 16 matrix clocks, two waves per SIMD:
 // 0.41 matrix-pipe busy.  Here every value is split ONCE, by eight splitter waves, into bf16-slice rings in LDS; the eight consumer
 // waves read ready 16-byte fragments and issue MFMAs:

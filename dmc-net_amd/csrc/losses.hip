@@ -361,9 +361,9 @@ int dmc_set_option(const char* name, int value) {
         return fail(DMC_E_INVALID, "dmc_set_option: '%s' switches parts of a kernel off (results wrong) and exists only in the -DDMC_MEASURE build", name);
     if (i == OPT_GRID_RESERVE_CUS && (value < 0 || value > 128))
         return fail(DMC_E_INVALID, "dmc_set_option: grid_reserve_cus = %d (0 .. 128 CUs may be left to other streams)", value);
-    if (!MEASURE_BUILD && !product_value(i, value))
-        return fail(DMC_E_INVALID, "dmc_set_option: %s = %d selects a kernel variant that lost its A/B measurement; it is compiled into the "
-                    "-DDMC_MEASURE build only", name, value);
+    if (!accepted_value(i, value))      // (only these three options refuse values: the option keeps the one it had)
+        return fail(DMC_E_INVALID, "dmc_set_option: %s = %d is not accepted (values: %s); the kernel variants that other values "
+                    "selected lost their A/B measurement and are removed", name, value, i == OPT_GEN_WGRAD_PATH ? "4, 5" : "0, 1");
     g_options[i].store(value, std::memory_order_relaxed);
     return DMC_OK;
 }

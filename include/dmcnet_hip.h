@@ -46,13 +46,12 @@ const char* dmc_last_error(void);
 /* Kernel-selection options for A/B measurements (tools/, bench.py); every default is the fastest measured path.
  *   "gen_fused"       1 (default): the generator forward as ONE launch (gen_fused.hip: strips of <= 118 columns walked row by row,
  *                     features line-buffered in LDS, the six layers pipelined across the waves of a workgroup; any H, W <= 224);
- *                     0: the layer-by-layer kernels, which also serve wider images.  [2 / 3 = also the one-launch data gradient,
- *                     gen_fused_bwd.hip: measured slower, -DDMC_MEASURE build only]
+ *                     0: the layer-by-layer kernels, which also serve wider images.  Bit 0 only: values 0 and 1.
  *   "gen_layer_path"  1 (default) / 0: matrix-core / VALU layer kernels of the layer-by-layer forward and the data gradient.
- *                     [3, 4, 5: tile variants that lost their measurement, -DDMC_MEASURE build only]
+ *                     Values 0 and 1.
  *   "gen_gather"      0: push form for the Cout-8 layers.        "gen_fuse45"  0: layers 4 and 5 as two launches.
  *   "gen_wgrad_path"  5 (default): the row-sliding weight gradient of gen_wgrad.hip (W % 4 == 0, else path 4's rules); 4: the bf16x3
- *                     tile kernel.  [0 .. 3: predecessors, -DDMC_MEASURE build only]
+ *                     tile kernel.  Values 4 and 5.
  *   "gen_fuse_fwd" / "gen_fuse_bwd"  0: the layer-by-layer forward / data-gradient launches instead of the fused groups.
  *   "gen_x3"          bit K: hidden layer K (0 .. 2) of the layer-by-layer forward in bf16x3 arithmetic (gen_x3.hip); default 2.
  *   "gen_wino"        bit K: hidden layer K (0 .. 3) of the layer-by-layer forward, bit 8 + K: data-gradient group K (0 .. 4), on the
@@ -70,8 +69,10 @@ const char* dmc_last_error(void);
  *   "gen_ablate" / "conv_ablate" (parts of a kernel switched off, results wrong), "gen_stagger": MEASUREMENT BUILD ONLY
  *                     (-DDMC_MEASURE, dmc-net_amd/build.py --measure -> libdmcnet_hip_measure.so): the product library refuses
  *                     them, they read 0 and the ablated paths are not compiled into its kernels.
- * The product library also refuses the option VALUES in [brackets] above (kernel variants that lost their A/B measurement are
- * compiled into the measurement build only).  dmc_get_option("measure_build") reads 1 in that build, 0 in the product library.
+ * "gen_fused", "gen_layer_path" and "gen_wgrad_path" accept the values named above and no others, in both builds (the kernel
+ * variants that further values once selected lost their A/B measurement and are removed); the error text names the option and its
+ * accepted values, and the option keeps the value it had.  dmc_get_option("measure_build") reads 1 in the measurement build, 0 in
+ * the product library.
  * dmc_set_option returns DMC_E_INVALID for an unknown name or a refused value; dmc_get_option returns -1 for an unknown name. */
 int dmc_set_option(const char* name, int value);
 int dmc_get_option(const char* name);

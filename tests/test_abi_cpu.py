@@ -130,19 +130,21 @@ def test_classifier_conv_entry_points_host_side_without_gpu():
     # generator kernel selection: layer 1 on gen_x3.hip, data-gradient groups 0 and 1 on the Winograd ring kernel;
     # the measurement-only options are off
     assert lib.dmc_get_option(b"gen_x3") == 2 and lib.dmc_get_option(b"gen_wino") == 0x300
-    assert lib.dmc_get_option(b"gen_fused") == 1                 # bit 0: the one-launch forward (csrc/gen_fused.hip); bit 1 (opt-in): the one-launch data gradient (gen_fused_bwd.hip)
+    assert lib.dmc_get_option(b"gen_fused") == 1                 # bit 0: the one-launch forward (csrc/gen_fused.hip)
     # the options that switch parts of a kernel off (results wrong) exist only in the -DDMC_MEASURE build: the product library
     # refuses to set them and reads them as 0 -- no option value can make it compute something else than the reference
     for name in (b"gen_ablate", b"gen_stagger", b"conv_ablate"):
         assert lib.dmc_get_option(name) == 0
         assert lib.dmc_set_option(name, 1) != 0 and b"DMC_MEASURE" in lib.dmc_last_error()
         assert lib.dmc_get_option(name) == 0
-    # kernel variants that lost their A/B measurement are compiled into the -DDMC_MEASURE build only (round 6): the product
-    # library refuses the option VALUES that select them and keeps the value it had
+    # kernel variants that lost their A/B measurement are removed: the library (either build) refuses the option VALUES that
+    # selected them, names the option in the error text and keeps the value it had
     assert lib.dmc_get_option(b"measure_build") == 0
     for name, bad, good in ((b"gen_fused", (2, 3), 1), (b"gen_layer_path", (3, 4, 5), 1), (b"gen_wgrad_path", (0, 1, 2, 3), 5)):
         for v in bad:
-            assert lib.dmc_set_option(name, v) != 0 and b"DMC_MEASURE" in lib.dmc_last_error(), (name, v)
+            assert lib.dmc_set_option(name, v) != 0, (name, v)
+            err = lib.dmc_last_error()
+            assert name in err and b"DMC_MEASURE" not in err, (name, v, err)
             assert lib.dmc_get_option(name) == good
         assert lib.dmc_set_option(name, good) == 0
     assert lib.dmc_set_option(b"gen_wgrad_path", 4) == 0 and lib.dmc_set_option(b"gen_wgrad_path", 5) == 0

@@ -1,5 +1,4 @@
-"""EstimatorDenseNetTiny forward as ONE launch (csrc/gen_fused.hip; option gen_fused bit 0, the default) and its data gradient as
-ONE launch (gen_fused_bwd.hip; bit 1, opt-in: measured slower than the five layer launches): strips of <= 118 columns
+"""EstimatorDenseNetTiny forward as ONE launch (csrc/gen_fused.hip; option gen_fused bit 0, the default): strips of <= 118 columns
 walked row by row, six layers pipelined across the waves of a workgroup.  The oracle / golden cases of tests/test_hip_parity.py
 run on it by default; here: the shapes its geometry cares about (one strip with one or two pixel halves, two strips with even
 and odd widths, images shorter than the pipeline, more strips than workgroups), the saved features the backward reads, the
@@ -24,14 +23,8 @@ def _set(name, value):
     return before
 
 
-def _all_fused():
-    """3 = the one-launch forward AND the one-launch data gradient: the latter lost its measurement and is compiled into the
-    -DDMC_MEASURE build only (DMC_HIP_LIB=.../libdmcnet_hip_measure.so); the product library serves bit 0 = the forward."""
-    return 3 if dmcnet_amd._lib.load().dmc_get_option(b"measure_build") == 1 else 1
-
-
 def test_fused_forward_is_the_default():
-    assert dmcnet_amd._lib.load().dmc_get_option(b"gen_fused") == 1      # bit 0: forward (default), bit 1: data gradient (opt-in)
+    assert dmcnet_amd._lib.load().dmc_get_option(b"gen_fused") == 1      # bit 0: the one-launch forward
 
 
 # widths: <= 62 one pixel half; 63 .. 118 two halves of one strip; 119 .. 224 two strips (odd widths: unequal strips);
@@ -39,11 +32,9 @@ def test_fused_forward_is_the_default():
 @pytest.mark.parametrize("shape", [(1, 5, 1, 1), (2, 5, 2, 3), (1, 5, 5, 62), (1, 5, 7, 63), (2, 5, 9, 64), (1, 5, 12, 117),
                                    (1, 5, 13, 118), (1, 5, 11, 119), (2, 5, 10, 120), (1, 5, 8, 121), (1, 5, 17, 223),
                                    (2, 5, 30, 224), (1, 5, 3, 224), (1, 5, 1, 224), (1, 5, 26, 180), (1, 5, 6, 225)])
-@pytest.mark.parametrize("delta,fused", [(False, 1), (True, 1), (True, 3)])
+@pytest.mark.parametrize("delta,fused", [(False, 1), (True, 1)])
 def test_fused_forward_edge_shapes(shape, delta, fused, request):
-    if fused == 3 and _all_fused() != 3:
-        pytest.skip("the one-launch data gradient exists in the -DDMC_MEASURE build only")
-    before = _set(b"gen_fused", fused)                 # 3: the one-launch data gradient too
+    before = _set(b"gen_fused", fused)
     request.addfinalizer(lambda: _set(b"gen_fused", before))
     o, m = tiny_pair(12)
     x = rnd(7, shape)
@@ -83,7 +74,7 @@ def test_fused_forward_saved_features_and_second_witness():
     y64 = o64.predict_flow(xin) + mv.double()
     ws, bs = m._params()
     got = {}
-    F = _all_fused()
+    F = 1
     for fused in (F, 0):
         before = _set(b"gen_fused", fused)
         try:
@@ -115,7 +106,7 @@ def test_fused_forward_full_frames_vs_fp64_and_determinism():
         y64 = o64(x.double()) + mv.double()
     loss64 = float(((y64 - flow.double()) ** 2).mean())
     runs = {}
-    F = _all_fused()
+    F = 1
     for fused in (F, F, 0):
         before = _set(b"gen_fused", fused)
         try:

@@ -1181,33 +1181,31 @@ def test_disc_block_unit(first, cin, cout, stride, use_bn, hw):
 
 
 @pytest.mark.gpu
-def test_generator_half_tile_variant_is_bit_identical():
-    """Option gen_layer_path: 5 = every ring layer on the three-stage single-workgroup kernel, 1 (default) = forward layer 2 on
-    the two-stage ring with two workgroups per CU, 4 = layers 2 and 3 so, 3 = layers 2 and 3 on 4-row tiles with two pixels
-    per lane.  The same products in the same order: the forward output and the backward's gradients are bitwise equal;
-    224 x 224 and an edge shape."""
+@pytest.mark.parametrize("n,h,w", [(2, 70, 92), (1, 12, 228)])
+def test_generator_layer_by_layer_ring_kernels_vs_oracle(n, h, w):
+    """The layer-by-layer kernels under the default gen_layer_path (option gen_fused = 0; W % 4 == 0: the ring kernels and the
+    forms that follow them): forward and the twelve parameter gradients against the CPU oracle at test_fused_forward_edge_shapes'
+    bars, two runs bitwise equal.  70 rows: a ragged last 8-row tile; 228 columns: wider than 224, the images this path serves
+    in production."""
     lib = dmcnet_amd._lib.load()
-    if lib.dmc_get_option(b"measure_build") != 1:
-        pytest.skip("gen_layer_path 3 / 4 / 5 select variants that lost their measurement: -DDMC_MEASURE build only (DMC_HIP_LIB)")
-    before = lib.dmc_get_option(b"gen_layer_path")
-    fused_before = lib.dmc_get_option(b"gen_fused")
-    dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_fused", 0), "dmc_set_option")       # (the layer-by-layer forward is what the option selects within)
+    before = lib.dmc_get_option(b"gen_fused")
+    dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_fused", 0), "dmc_set_option")
     try:
-        for (n, h, w) in ((5, 224, 224), (2, 70, 92)):
-            torch.manual_seed(3)
-            m = dmcnet_amd.model.EstimatorDenseNetTiny(5).to(DEV)
-            mv, res = torch.randn(n, 2, h, w, device=DEV), torch.randn(n, 3, h, w, device=DEV)
-            go = torch.randn(n, 2, h, w, device=DEV)
-            outs = []
-            for path in (5, 1, 3, 4):
-                dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_layer_path", path), "dmc_set_option")
-                m.zero_grad(set_to_none=True)
-                y = m.forward_mv_res(mv, res, True)
-                y.backward(go)
-                outs.append([y.detach()] + [p.grad.clone() for p in m.parameters()])
-            for other in outs[1:]:
-                for a, b in zip(outs[0], other):
-                    assert torch.equal(a, b)
+        o, m = tiny_pair(12)
+        x, r = rnd(7, (n, 5, h, w)), rnd(8, (n, 2, h, w))
+        yo = o(x) + x[:, :2]
+        (yo * r).sum().backward()
+        runs = []
+        for _ in range(2):
+            m.zero_grad(set_to_none=True)
+            y = m.forward_mv_res(x[:, :2].contiguous().to(DEV), x[:, 2:].contiguous().to(DEV), add_mv=True)
+            (y * r.to(DEV)).sum().backward()
+            runs.append([y.detach().clone()] + [p.grad.clone() for p in m.parameters()])
     finally:
-        dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_layer_path", before), "dmc_set_option")
-        dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_fused", fused_before), "dmc_set_option")
+        dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_fused", before), "dmc_set_option")
+    assert len(runs[0]) == 13
+    assert rel_err(runs[0][0], yo) < 1e-5
+    for (k, po), g in zip(o.named_parameters(), runs[0][1:]):
+        assert rel_err(g, po.grad) < 1e-4, k
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)

@@ -190,9 +190,9 @@ def _generic_case(seed, frames):
 
 
 # (seed, frames, backward selection): the five data seeds of tools/gen_flip_lottery.py at 16 frames each for the default backward and
-# for every data-gradient group on the Winograd kernel (mask 0x1F00); the one-launch data gradient (-1) on two seeds; the full
+# for every data-gradient group on the Winograd kernel (mask 0x1F00); the full
 # 120-frame batch once.  (16 frames = 0.8 M pixels per seed: the CPU side -- one fp32 and three fp64 passes -- sets the run time.)
-GENERIC_CASES = ([(s, 16, m) for s in (23, 24, 25, 26, 27) for m in (0x300, 0x1F00)] + [(23, 16, -1), (24, 16, -1), (23, 120, 0x300)])
+GENERIC_CASES = ([(s, 16, m) for s in (23, 24, 25, 26, 27) for m in (0x300, 0x1F00)] + [(23, 120, 0x300)])
 
 
 @pytest.mark.parametrize("seed,frames,backward_mask", GENERIC_CASES)
@@ -208,20 +208,14 @@ def test_generator_full_batch_generic_weights(seed, frames, backward_mask):
     from tests.gen_conditioned import conditioned_report
     o, o64, m, x, r = _generic_case(seed, frames)
     lib = dmcnet_amd._lib.load()
-    before, fused_before = lib.dmc_get_option(b"gen_wino"), lib.dmc_get_option(b"gen_fused")
-    if backward_mask < 0:          # the five data-gradient groups as one launch (csrc/gen_fused_bwd.hip, option gen_fused bit 1)
-        if lib.dmc_get_option(b"measure_build") != 1:
-            pytest.skip("the one-launch data gradient lost its measurement: -DDMC_MEASURE build only (DMC_HIP_LIB)")
-        dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_fused", 3), "dmc_set_option")
-    else:
-        dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_wino", backward_mask), "dmc_set_option")
+    before = lib.dmc_get_option(b"gen_wino")
+    dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_wino", backward_mask), "dmc_set_option")
     try:
         y = m.forward_mv_res(x[:, :2].contiguous().to(DEV), x[:, 2:].contiguous().to(DEV), add_mv=True)
         saved = y.grad_fn.saved_tensors[2].view(frames, 28, 224, 224)
         (y * r.to(DEV)).sum().backward()
     finally:
         dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_wino", before), "dmc_set_option")
-        dmcnet_amd._lib.check(lib.dmc_set_option(b"gen_fused", fused_before), "dmc_set_option")
     rep = conditioned_report(o, o64, x, r, y.detach(), [p.grad for p in m.parameters()], saved)
     print("seed %d, %d frames: sign disagreements with fp64: device %d, oracle %d; output error %.2e (oracle %.2e)"
           % (seed, frames, rep["flips_hip"], rep["flips_ref"], rep["e_out_hip"], rep["e_out_ref"]))

@@ -15,7 +15,7 @@ for p in 4 5; do
 import json
 d = json.loads(open("$OUT/wab_$p.json").read().strip().splitlines()[-1])
 k = [l for l in open("$OUT/wab_${p}_region.csv") if "gen_wgrad_rs_kernel" in l or "gen_bwd_weight_pc_kernel" in l][0].split(",")
-print("gen_wgrad_path $p: step %.3f ms (median %.3f); %s %.1f us in the timed region" % (d["ms_per_step"], d["ms_per_step_median"], "gen_wgrad_rs_kernel" if $p == 5 else "gen_bwd_weight_pc_kernel<3>", float(k[-5]) / 1e3))
+print("gen_wgrad_path $p: step %.3f ms (median %.3f); %s %.1f us in the timed region" % (d["ms_per_step"], d["ms_per_step_median"], "gen_wgrad_rs_kernel" if $p == 5 else "gen_bwd_weight_pc_kernel", float(k[-5]) / 1e3))
 PY
 done
 done
