@@ -167,6 +167,12 @@ SIGNATURES = {
     "dmc_mv_from_accu": (_I, [_P, _P, _I, _I, _P]),
     "dmc_residual": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "dmc_mv_gop_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "dmc_ctx_unit_supported": (_I, [_I] * 6),
+    "dmc_ctx_wpack_bytes": (_Z, [_I, _I]),
+    "dmc_ctx_pack_weights": (_I, [_P, _P, _I, _I, _P]),
+    "dmc_ctx_unit_eval": (_I, [_P] * 6 + [_I] * 6 + [_P]),
+    "dmc_ctx_first_eval": (_I, [_P] * 6 + [_I] * 3 + [_P]),
+    "dmc_ctx_heads_eval": (_I, [_P] * 11 + [_I] * 3 + [_P]),
 }
 
 _lib = None

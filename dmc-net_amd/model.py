@@ -6,15 +6,23 @@ Same constructor, attribute names (``base_model``, ``gen_flow_model``, ``discrim
 code/dmcnet_GAN/model.py:442-585 (paths relative to the reference root).  What differs is
 where the arithmetic runs: the DenseNetTiny generator (+ cat + delta add), the ResNet's
 convolutions / BatchNorms / stem (``resnet.py`` -> ``ops.conv_bn_act``, ``ops.stem_conv``, ...) and
-the Discriminator3 blocks (``ops.disc_block``) are hand-written HIP kernels behind the C ABI; only
-the API-only estimator / discriminator variants and the two ``nn.Linear`` heads stay on
-PyTorch-ROCm ops.  Passing ``arch_d`` selects the GAN variant.
+the Discriminator3 blocks (``ops.disc_block``) are hand-written HIP kernels behind the C ABI, and so
+are ContextNetwork / ContextNetworkAtt in eval mode (``ops.context_eval``); only the API-only
+estimator / discriminator variants, the training of the ContextNetworks and the two ``nn.Linear``
+heads stay on PyTorch-ROCm ops.  Passing ``arch_d`` selects the GAN variant.
 """
+import os as _os
+
 import torch
 from torch import nn
 import torch.nn.functional as F
 
 from . import ops, resnet, transforms
+
+#: ContextNetwork / ContextNetworkAtt under eval() + no_grad run on the kernels of csrc/ctx_eval.hip (ops.context_eval: one launch
+#: per dilated conv + BatchNorm + LeakyReLU unit) whenever ops.context_eval_supported accepts the network and the input.
+#: DMC_CTX_EVAL=0 (read once, here): always the stock modules -- A/B measurements, and a safety valve.
+CTX_EVAL = _os.environ.get("DMC_CTX_EVAL", "1") != "0"
 
 # ---------------------------------------------------------------------------- generators
 
@@ -138,6 +146,8 @@ class ContextNetwork(nn.Module):
         self.conv_context = nn.Sequential(*[_dilated_unit(a, b, d, batch_norm) for a, b, d in plan])
 
     def forward(self, x):
+        if CTX_EVAL and ops.context_eval_supported(self, x):
+            return ops.context_eval(self, x)
         return self.conv_context(x)
 
 
@@ -156,6 +166,8 @@ class ContextNetworkAtt(nn.Module):
         self.predict_att = nn.Sequential(_dilated_unit(32, 2, 1, batch_norm), nn.ReLU(inplace=False))
 
     def forward(self, x):
+        if CTX_EVAL and ops.context_eval_supported(self, x):
+            return ops.context_eval(self, x)
         x = self.conv_context(x)
         return self.predict_flow(x), self.predict_att(x)
 

@@ -2580,3 +2580,150 @@ def stem3d_bn_relu_eval(x, conv, bn, relu=True):
                                                 _lib.ptr(bn.running_var), float(bn.eps), _lib.ptr(work), _lib.ptr(out), n, t, h, w,
                                                 int(relu), _stream()), "dmc_stem3d_bf16_fwd_eval")
     return out
+
+
+# ---- ContextNetwork / ContextNetworkAtt in eval mode: one launch per dilated conv + BatchNorm + LeakyReLU unit (csrc/ctx_eval.hip) ----
+
+_CTX_MAX_INDEX = 1 << 31       # one launch indexes frames * H * W * 128 (the widest activation) below this
+_CTX_SLOPE = 0.1
+
+
+def context_eval_chunks(n, h, w):
+    """Frame ranges [(a, b), ...] of the launches that evaluate ``n`` frames of ``h`` x ``w``: they tile [0, n) in order and each
+    keeps frames * h * w * 128 below 2^31 (what dmc_ctx_unit_supported accepts).  A pure function of its arguments."""
+    n, h, w = int(n), int(h), int(w)
+    if n <= 0 or h <= 0 or w <= 0:
+        raise ValueError("context_eval_chunks: sizes must be positive")
+    per = (_CTX_MAX_INDEX - 1) // (h * w * 128)
+    if per <= 0:
+        raise ValueError("context_eval_chunks: one %d x %d frame is more than a launch can index" % (h, w))
+    return [(a, min(a + per, n)) for a in range(0, n, per)]
+
+
+def _ctx_unit_parts(unit, dilation=None):
+    """(conv, bn) of a Sequential(Conv2d 3x3 dilated no-bias, BatchNorm2d eval, LeakyReLU(0.1)), or None."""
+    if not isinstance(unit, torch.nn.Sequential) or len(unit) != 3:
+        return None
+    conv, bn, act = unit[0], unit[1], unit[2]
+    if not (isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.BatchNorm2d) and isinstance(act, torch.nn.LeakyReLU)):
+        return None
+    if abs(act.negative_slope - _CTX_SLOPE) > 1e-12:
+        return None
+    if conv.bias is not None or conv.groups != 1 or conv.padding_mode != "zeros" or tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1):
+        return None
+    if conv.dilation[0] != conv.dilation[1] or tuple(conv.padding) != tuple(conv.dilation):
+        return None
+    if dilation is not None and conv.dilation[0] != dilation:
+        return None
+    if bn.training or not bn.track_running_stats or not bn.affine or bn.running_mean is None:
+        return None
+    if not (conv.weight.is_cuda and bn.weight.is_cuda and bn.running_mean.is_cuda):
+        return None
+    if conv.weight.dtype != torch.float32 or bn.weight.dtype != torch.float32 or bn.running_mean.dtype != torch.float32:
+        return None
+    return conv, bn
+
+
+def _ctx_plan(net):
+    """(trunk [(conv, bn), ...], flow (conv, bn), att (conv, bn) | None) of a ContextNetwork / ContextNetworkAtt whose every unit
+    the eval kernels serve, or None."""
+    trunk = getattr(net, "conv_context", None)
+    if not isinstance(trunk, torch.nn.Sequential):
+        return None
+    units = list(trunk)
+    att = None
+    if hasattr(net, "predict_att"):
+        pa = net.predict_att
+        if not (isinstance(pa, torch.nn.Sequential) and len(pa) == 2 and isinstance(pa[1], torch.nn.ReLU)):
+            return None
+        flow, att = _ctx_unit_parts(net.predict_flow, 1), _ctx_unit_parts(pa[0], 1)
+        if flow is None or att is None:
+            return None
+    else:
+        if len(units) < 2:
+            return None
+        flow = _ctx_unit_parts(units.pop(), 1)
+        if flow is None:
+            return None
+    parts = [_ctx_unit_parts(u) for u in units]
+    if not parts or any(p is None for p in parts):
+        return None
+    c = 5
+    for conv, _ in parts:
+        if conv.in_channels != c:
+            return None
+        c = conv.out_channels
+    heads = [flow] + ([att] if att is not None else [])
+    if parts[0][0].dilation[0] != 1 or any(h[0].in_channels != c or h[0].out_channels != 2 for h in heads) or c != 32:
+        return None
+    return parts, flow, att
+
+
+def context_eval_supported(net, x):
+    """True if ``net`` (model.ContextNetwork / ContextNetworkAtt, batch_norm=True, every BatchNorm in eval mode) can be evaluated
+    on ``x`` by this package's kernels: no autograd, a CUDA fp32 [N, 5, H, W] input, every unit of the expected form and accepted
+    by dmc_ctx_unit_supported (code/dmcnet/model.py:45-104 under model.eval() + no_grad)."""
+    if torch.is_grad_enabled():
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 5 and x.numel() > 0):
+        return False
+    plan = _ctx_plan(net)
+    if plan is None:
+        return False
+    n, _, h, w = x.shape
+    try:
+        a, b = context_eval_chunks(n, h, w)[0]
+    except ValueError:
+        return False
+    lib = _lib.load()
+    parts, flow, _ = plan
+    return all(lib.dmc_ctx_unit_supported(b - a, h, w, conv.in_channels, conv.out_channels, conv.dilation[0]) for conv, _ in parts + [flow])
+
+
+def context_eval(net, x):
+    """``net(x)`` of a ContextNetwork (-> gen_flow [N, 2, H, W]) or ContextNetworkAtt (-> (gen_flow, att_flow)) in eval mode on
+    the kernels of csrc/ctx_eval.hip: seven launches per frame range (context_eval_chunks), NHWC fp32 between the units, the
+    weights of the middle units split into bf16 slices once per call.  Requires context_eval_supported(net, x)."""
+    lib = _lib.load()
+    if not context_eval_supported(net, x):
+        raise _lib.DmcHipError("context_eval: the network or the input is not served by the eval kernels (context_eval_supported)")
+    parts, flow, att = _ctx_plan(net)
+    x = x.contiguous()
+    n, _, h, w = x.shape
+    dev = x.device
+    s = _stream()
+    with _span("context_eval"):
+        bns = [(_bn_eval_stats(bn), bn.weight.detach().contiguous(), bn.bias.detach().contiguous()) for _, bn in parts]
+        w_first = parts[0][0].weight.detach().contiguous()
+        packs = []
+        for conv, _ in parts[1:]:
+            cin, cout = conv.in_channels, conv.out_channels
+            wp = torch.empty(lib.dmc_ctx_wpack_bytes(cin, cout), dtype=torch.uint8, device=dev)
+            _lib.check(lib.dmc_ctx_pack_weights(_lib.ptr(conv.weight.detach().permute(0, 2, 3, 1).contiguous()), _lib.ptr(wp), cin, cout, s),
+                       "dmc_ctx_pack_weights")
+            packs.append(wp)
+        heads = []
+        for conv, bn in [flow] + ([att] if att is not None else []):
+            heads.append((conv.weight.detach().permute(0, 2, 3, 1).contiguous(), _bn_eval_stats(bn), bn.weight.detach().contiguous(),
+                          bn.bias.detach().contiguous()))
+        out_flow = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        out_att = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev) if att is not None else None
+        for a, b in context_eval_chunks(n, h, w):
+            f = b - a
+            cur = torch.empty((f, h, w, 32), dtype=torch.float32, device=dev)
+            st, g, be = bns[0]
+            _lib.check(lib.dmc_ctx_first_eval(_lib.ptr(x[a:b]), _lib.ptr(w_first), _lib.ptr(st), _lib.ptr(g), _lib.ptr(be), _lib.ptr(cur),
+                                              f, h, w, s), "dmc_ctx_first_eval")
+            for (conv, _), wp, (st, g, be) in zip(parts[1:], packs, bns[1:]):
+                nxt = torch.empty((f, h, w, conv.out_channels), dtype=torch.float32, device=dev)
+                _lib.check(lib.dmc_ctx_unit_eval(_lib.ptr(cur), _lib.ptr(wp), _lib.ptr(st), _lib.ptr(g), _lib.ptr(be), _lib.ptr(nxt), f, h, w,
+                                                 conv.in_channels, conv.out_channels, conv.dilation[0], s), "dmc_ctx_unit_eval")
+                cur = nxt
+            hf = heads[0]
+            ha = heads[1] if att is not None else (None, None, None, None)
+            _lib.check(lib.dmc_ctx_heads_eval(_lib.ptr(cur), _lib.ptr(hf[0]), _lib.ptr(hf[1]), _lib.ptr(hf[2]), _lib.ptr(hf[3]),
+                                              _lib.ptr(ha[0]), _lib.ptr(ha[1]), _lib.ptr(ha[2]), _lib.ptr(ha[3]), _lib.ptr(out_flow[a:b]),
+                                              _lib.ptr(out_att[a:b]) if att is not None else None, f, h, w, s), "dmc_ctx_heads_eval")
+    if att is not None:
+        return out_flow, out_att
+    return out_flow

@@ -832,6 +832,35 @@ int dmc_mv_gop_batch(const void* mvs, int mv_stride, int n_mv, const int32_t* fr
                      int n_chains, const int32_t* emit, int32_t* owner_ws, const uint8_t* bgr_ref, const uint8_t* bgr_cur,
                      int32_t* accu_out, int32_t* mv_out, int32_t* res_out, int32_t* bad_source, int H, int W, dmc_stream_t stream);
 
+/* ---- ContextNetwork / ContextNetworkAtt in eval mode (csrc/ctx_eval.hip) ----
+ * Replaces: the units Conv2d(3x3, dilation d, padding d, bias=False) -> BatchNorm2d (running statistics) -> LeakyReLU(0.1) of
+ *           code/dmcnet/model.py:45-104 as the evaluator runs them under model.eval() + no_grad; one launch per unit, the
+ *           normalisation and the activation in the convolution's epilogue.  Activations between units are NHWC fp32.
+ * BatchNorm: stats = mean[C], 1 / sqrt(var + eps)[C]; gamma[C], beta[C].  Result = leaky((conv - mean) * invstd * gamma + beta).
+ * dmc_ctx_unit_supported: 1 for the first unit (Cin 5, Cout 32, dilation 1), the heads (Cin 32, Cout 2, dilation 1) and the
+ *   middle units (Cin, Cout in {32, 64, 96, 128}, dilation in {1, 2, 4, 8, 16}) when N, H, W > 0 and N * H * W * 128 < 2^31
+ *   (what one launch indexes; the caller splits larger batches into frame ranges), else 0.
+ * dmc_ctx_pack_weights: w OHWI [Cout][3][3][Cin] fp32 -> wpack, dmc_ctx_wpack_bytes() bytes (three bf16 slices,
+ *   [tap][Cin / 16][slice][Cout][16]; 0 for an unsupported channel pair).
+ * dmc_ctx_unit_eval: a middle unit, x NHWC [N][H][W][Cin] -> y NHWC [N][H][W][Cout]; bf16x3 arithmetic on the matrix cores.
+ * dmc_ctx_first_eval: the first unit, x NCHW [N][5][H][W], w OIHW [32][5][3][3] (the module's weight as stored) -> y NHWC
+ *   [N][H][W][32]; fp32 FMAs in a fixed order.
+ * dmc_ctx_heads_eval: x NHWC [N][H][W][32], w_flow / w_att OHWI [2][3][3][32] -> flow NCHW [N][2][H][W] and, when w_att is
+ *   given, att NCHW [N][2][H][W] = max(unit(x), 0), both heads in one launch.  w_att == NULL: one head, att must be NULL.
+ * Deterministic, no atomics, independent of the batch a frame is in; inputs are read only.
+ * DMC_E_INVALID before any launch (nothing written): a NULL pointer (the attention group excepted, all or none), a shape
+ * outside dmc_ctx_unit_supported(). */
+int dmc_ctx_unit_supported(int N, int H, int W, int Cin, int Cout, int dilation);
+size_t dmc_ctx_wpack_bytes(int Cin, int Cout);
+int dmc_ctx_pack_weights(const float* w, void* wpack, int Cin, int Cout, dmc_stream_t stream);
+int dmc_ctx_unit_eval(const float* x, const void* wpack, const float* stats, const float* gamma, const float* beta, float* y,
+                      int N, int H, int W, int Cin, int Cout, int dilation, dmc_stream_t stream);
+int dmc_ctx_first_eval(const float* x, const float* w, const float* stats, const float* gamma, const float* beta, float* y,
+                       int N, int H, int W, dmc_stream_t stream);
+int dmc_ctx_heads_eval(const float* x, const float* w_flow, const float* stats_flow, const float* gamma_flow, const float* beta_flow,
+                       const float* w_att, const float* stats_att, const float* gamma_att, const float* beta_att, float* flow,
+                       float* att, int N, int H, int W, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
