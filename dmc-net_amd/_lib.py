@@ -173,6 +173,12 @@ SIGNATURES = {
     "dmc_ctx_unit_eval": (_I, [_P] * 6 + [_I] * 6 + [_P]),
     "dmc_ctx_first_eval": (_I, [_P] * 6 + [_I] * 3 + [_P]),
     "dmc_ctx_heads_eval": (_I, [_P] * 11 + [_I] * 3 + [_P]),
+    "dmc_dconv_supported": (_I, [_I] * 6),
+    "dmc_dconv_wpack_bytes": (_Z, [_I, _I]),
+    "dmc_dconv_wgrad_workspace_bytes": (_Z, [_I] * 5),
+    "dmc_dconv_pack_weights": (_I, [_P, _P, _I, _I, _I, _P]),
+    "dmc_dconv_fwd": (_I, [_P] * 3 + [_I] * 6 + [_P]),
+    "dmc_dconv_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
 }
 
 _lib = None

@@ -19,7 +19,7 @@
 //   * The B fragment of a 32x32x16 MFMA is, per lane, 8 consecutive channels of ONE pixel: 32 contiguous bytes of the
 //     NHWC tensor.  Each lane gathers its own fragment from global memory into registers (two 16-byte loads, one step
 //     ahead) and splits it there; activations never pass through the LDS, so how far a tap reaches costs nothing.
-//   * Weights are split once per call (ctx_pack_kernel) into [tap][k-block][slice][co][16] bf16: the three slices of a
+//   * Weights are split once per call (pack_kernel, ctx_common.h) into [tap][k-block][slice][co][16] bf16: the three slices of a
 //     step's [Cout][16] panel are one contiguous chunk of 96 Cout bytes, copied global -> registers -> LDS by the whole
 //     workgroup one step ahead (two buffers, one barrier per step), read by every wave as conflict-free ds_read_b128
 //     (a wave's 64 lanes cover 2 KB of consecutive addresses).
@@ -28,27 +28,21 @@
 // No atomics; a pixel's sum is formed in one fixed order by one lane column of the matrix core, whatever tile or batch
 // the pixel is in: results are bit-identical from run to run and independent of the batch.
 // All tensor offsets are 64-bit; dmc_ctx_unit_supported() bounds N H W so that the pixel index fits an int.
-#include "dmc_common.h"
+#include "ctx_common.h"
 
 using namespace dmc;
+using namespace dmc::ctxk;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr float SLOPE = 0.1f;
 
 struct CtxArgs {
-    const float* x;                 // [N][H][W][Cin]
-    const unsigned short* wpack;    // [9][Cin / 16][3][Cout][16] bf16
+    GatherArgs g;                   // x [N][H][W][Cin], wpack [9][Cin / 16][3][Cout][16] bf16, the geometry
     const float* stats;             // mean[Cout], invstd[Cout]
     const float* gamma;
     const float* beta;
     float* y;                       // [N][H][W][Cout]
-    int N, H, W, Cin, d, M;         // M = N H W
 };
 
 __device__ __forceinline__ float bn_leaky(float v, float mean, float istd, float gamma, float beta) {
@@ -56,127 +50,15 @@ __device__ __forceinline__ float bn_leaky(float v, float mean, float istd, float
     return t > 0.f ? t : SLOPE * t;
 }
 
-// the three bf16 slices (truncating split, as conv_nhwc.hip's split_bf16x3) of 8 consecutive values
-struct Split3 { u32x4 s[3]; };
-__device__ __forceinline__ Split3 split3(const f32x4& lo, const f32x4& hi) {
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x3s_split3(v[e], u0[e], u1[e], u2[e]);
-    Split3 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        r.s[0][e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
-        r.s[1][e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
-        r.s[2][e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
-    }
-    return r;
-}
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
+// main loop: ctx_common.h's gather_gemm (shared with the raw convolution of dconv.hip); the epilogue is this kernel's
 template <int TN, int TM>
 __global__ __launch_bounds__(256) void ctx_unit_kernel(CtxArgs a) {
     constexpr int COUT = 32 * TN;
-    constexpr int CH = 3 * COUT * 32;                      // bytes of one step's weight chunk (three slices of [COUT][16] bf16)
-    constexpr int NWR = (CH + 4095) / 4096;                // 16-byte pieces per thread
-    __shared__ __attribute__((aligned(16))) char lds[2 * CH];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, khalf = lane >> 5;
-    const int m0 = blockIdx.x * (128 * TM) + wave * (32 * TM);
-
-    // ---- this lane's pixels: offset of (n, y, x, 8 khalf) and the taps that fall inside the frame ----
-    long xbase[TM];
-    unsigned tmask[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + 32 * i + l31;
-        xbase[i] = 0; tmask[i] = 0;
-        if (m < a.M) {
-            const int hw = a.H * a.W;
-            const int rem = m % hw;
-            const int yy = rem / a.W, xx = rem - yy * a.W;
-            xbase[i] = (long)m * a.Cin + 8 * khalf;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int iy = yy + (t / 3 - 1) * a.d, ix = xx + (t % 3 - 1) * a.d;
-                if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) tmask[i] |= 1u << t;
-            }
-        }
-    }
-
-    const int nkb = a.Cin >> 4;
-    const int nsteps = 9 * nkb;
-    int tap = 0, kb = 0;                                   // of the step being LOADED
-    f32x4 xlo[TM], xhi[TM];
-    u32x4 wr[NWR];
-    auto load_step = [&](int s) {
-        const int dy = (tap / 3 - 1) * a.d, dx = (tap % 3 - 1) * a.d;
-        const long toff = ((long)dy * a.W + dx) * a.Cin + 16 * kb;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const bool ok = (tmask[i] >> tap) & 1;
-            const float* p = a.x + (ok ? xbase[i] + toff : 0);
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(p), hi = *reinterpret_cast<const f32x4*>(p + 4);
-            xlo[i] = ok ? lo : (f32x4){0.f, 0.f, 0.f, 0.f};
-            xhi[i] = ok ? hi : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-        const char* src = reinterpret_cast<const char*>(a.wpack) + (long)s * CH;
-#pragma unroll
-        for (int r = 0; r < NWR; ++r) {
-            const int o = (r * 256 + tid) * 16;
-            if (CH % 4096 == 0 || o < CH) wr[r] = *reinterpret_cast<const u32x4*>(src + o);
-        }
-        if (++kb == nkb) { kb = 0; ++tap; }
-    };
-    auto store_w = [&](int buf) {
-#pragma unroll
-        for (int r = 0; r < NWR; ++r) {
-            const int o = (r * 256 + tid) * 16;
-            if (CH % 4096 == 0 || o < CH) *reinterpret_cast<u32x4*>(lds + buf * CH + o) = wr[r];
-        }
-    };
-
+    __shared__ __attribute__((aligned(16))) char lds[GatherLds<TN>::BYTES];
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int foff = l31 * 32 + khalf * 16;                // this lane's fragment inside a [32][16] bf16 panel
-
-    load_step(0);
-    store_w(0);
-    __syncthreads();
-#pragma unroll 1
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
-        Split3 xs[TM];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) xs[i] = split3(xlo[i], xhi[i]);
-        if (s + 1 < nsteps) load_step(s + 1);              // in flight during the MFMAs below
-        const char* wb = lds + buf * CH + foff;
-        // the six slice products, grouped by weight slice: (0,2) (0,1) (0,0) | (1,1) (1,0) | (2,0)
-#pragma unroll
-        for (int wsl = 0; wsl < 3; ++wsl) {
-            u32x4 wf[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) wf[j] = *reinterpret_cast<const u32x4*>(wb + (wsl * COUT + 32 * j) * 32);
-#pragma unroll
-            for (int xsl = 2 - wsl; xsl >= 0; --xsl)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = mfma_bf16(wf[j], xs[i].s[xsl], acc[i][j]);
-        }
-        if (s + 1 < nsteps) store_w(buf ^ 1);              // nobody reads that buffer during this step
-        __syncthreads();
-    }
+    const int m0 = gather_gemm<TN, TM>(a.g, lds, acc);
+    const int lane = threadIdx.x & 63;
+    const int l31 = lane & 31, khalf = lane >> 5;
 
     // ---- epilogue: lane holds pixel l31 of tile i, channels 32 j + 8 gq + 4 khalf + e in acc[i][j][4 gq + e] ----
 #pragma unroll
@@ -191,29 +73,13 @@ __global__ __launch_bounds__(256) void ctx_unit_kernel(CtxArgs a) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int m = m0 + 32 * i + l31;
-                if (m >= a.M) continue;
+                if (m >= a.g.M) continue;
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = bn_leaky(acc[i][j][4 * gq + e], mean[e], istd[e], gam[e], bet[e]);
                 *reinterpret_cast<f32x4*>(a.y + (long)m * COUT + co) = v;
             }
         }
-}
-
-// w [Cout][9][Cin] fp32 -> wpack [9][Cin / 16][3][Cout][16] bf16 slices
-__global__ __launch_bounds__(256) void ctx_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int Cin, int Cout) {
-    const int total = Cout * 9 * Cin;
-    const int nkb = Cin >> 4;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int ci = i % Cin, tap = (i / Cin) % 9, co = i / (9 * Cin);
-        unsigned u0, u1, u2;
-        x3s_split3(w[i], u0, u1, u2);
-        const long panel = ((long)(tap * nkb + (ci >> 4)) * 3) * Cout;      // in rows of 16
-        const long o = (panel + co) * 16 + (ci & 15);
-        wp[o] = (unsigned short)(u0 >> 16);
-        wp[o + (long)Cout * 16] = (unsigned short)(u1 >> 16);
-        wp[o + (long)Cout * 32] = (unsigned short)(u2 >> 16);
-    }
 }
 
 // ---- first unit: x NCHW [N][5][H][W], w OIHW [32][5][3][3] -> y NHWC [N][H][W][32]; one thread per pixel,
@@ -313,18 +179,12 @@ __global__ __launch_bounds__(256) void ctx_heads_kernel(HeadArgs a) {
     }
 }
 
-bool dilation_ok(int d) { return d == 1 || d == 2 || d == 4 || d == 8 || d == 16; }
-bool width_ok(int c) { return c == 32 || c == 64 || c == 96 || c == 128; }
-bool middle_ok(int Cin, int Cout, int d) { return width_ok(Cin) && width_ok(Cout) && dilation_ok(d); }
-
 }  // namespace
 
 extern "C" {
 
 int dmc_ctx_unit_supported(int N, int H, int W, int Cin, int Cout, int dilation) {
-    if (N <= 0 || H <= 0 || W <= 0) return 0;
-    // one launch indexes pixels (and the tile rows past the last one) with an int and the widest tensor with 31 bits
-    if ((long long)N * H * W * 128 >= (1ll << 31)) return 0;
+    if (!index_ok(N, H, W)) return 0;
     if (Cin == 5 && Cout == 32) return dilation == 1;       // the first unit
     if (Cin == 32 && Cout == 2) return dilation == 1;       // the head(s)
     return middle_ok(Cin, Cout, dilation) ? 1 : 0;
@@ -339,7 +199,7 @@ int dmc_ctx_pack_weights(const float* w, void* wpack, int Cin, int Cout, dmc_str
     if (!w || !wpack) return fail(DMC_E_INVALID, "dmc_ctx_pack_weights: null pointer");
     if (!width_ok(Cin) || !width_ok(Cout)) return fail(DMC_E_INVALID, "dmc_ctx_pack_weights: unsupported shape (Cin %d, Cout %d)", Cin, Cout);
     const int total = Cin * Cout * 9;
-    ctx_pack_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(w, reinterpret_cast<unsigned short*>(wpack), Cin, Cout);
+    pack_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(w, reinterpret_cast<unsigned short*>(wpack), Cin, Cout, 0);
     return check_launch("dmc_ctx_pack_weights");
 }
 
@@ -349,10 +209,10 @@ int dmc_ctx_unit_eval(const float* x, const void* wpack, const float* stats, con
     if (!middle_ok(Cin, Cout, dilation) || !dmc_ctx_unit_supported(N, H, W, Cin, Cout, dilation))
         return fail(DMC_E_INVALID, "dmc_ctx_unit_eval: unsupported shape (N %d, H %d, W %d, Cin %d, Cout %d, dilation %d)", N, H, W, Cin, Cout, dilation);
     CtxArgs a;
-    a.x = x; a.wpack = reinterpret_cast<const unsigned short*>(wpack); a.stats = stats; a.gamma = gamma; a.beta = beta; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.d = dilation; a.M = N * H * W;
+    a.g.x = x; a.g.wpack = reinterpret_cast<const unsigned short*>(wpack); a.stats = stats; a.gamma = gamma; a.beta = beta; a.y = y;
+    a.g.N = N; a.g.H = H; a.g.W = W; a.g.Cin = Cin; a.g.d = dilation; a.g.M = N * H * W;
     constexpr int TM = 2;
-    const dim3 grid((a.M + 128 * TM - 1) / (128 * TM));
+    const dim3 grid((a.g.M + 128 * TM - 1) / (128 * TM));
     hipStream_t s = (hipStream_t)stream;
     switch (Cout) {
         case 128: ctx_unit_kernel<4, TM><<<grid, 256, 0, s>>>(a); break;

@@ -8,8 +8,12 @@ where the arithmetic runs: the DenseNetTiny generator (+ cat + delta add), the R
 convolutions / BatchNorms / stem (``resnet.py`` -> ``ops.conv_bn_act``, ``ops.stem_conv``, ...) and
 the Discriminator3 blocks (``ops.disc_block``) are hand-written HIP kernels behind the C ABI, and so
 are ContextNetwork / ContextNetworkAtt in eval mode (``ops.context_eval``); only the API-only
-estimator / discriminator variants, the training of the ContextNetworks and the two ``nn.Linear``
-heads stay on PyTorch-ROCm ops.  Passing ``arch_d`` selects the GAN variant.
+estimator / discriminator variants, by default the training of the ContextNetworks, and the two
+``nn.Linear`` heads stay on PyTorch-ROCm ops.  With ``DMC_CTX_TRAIN=1`` (``CTX_TRAIN``, off by default)
+the dilated convolutions of the ContextNetworks' five middle units -- forward, data gradient and weight
+gradient, 99.4 % of the arithmetic -- run on csrc/dconv.hip (``ops.dilated_conv``) in training as well;
+their BatchNorms, LeakyReLUs, first unit and head(s) remain the stock modules.  Passing ``arch_d``
+selects the GAN variant.
 """
 import os as _os
 
@@ -23,6 +27,11 @@ from . import ops, resnet, transforms
 #: per dilated conv + BatchNorm + LeakyReLU unit) whenever ops.context_eval_supported accepts the network and the input.
 #: DMC_CTX_EVAL=0 (read once, here): always the stock modules -- A/B measurements, and a safety valve.
 CTX_EVAL = _os.environ.get("DMC_CTX_EVAL", "1") != "0"
+#: DMC_CTX_TRAIN=1 (read once, here; default 0): with autograd enabled, the convolutions of the five middle units of ContextNetwork /
+#: ContextNetworkAtt run on the kernels of csrc/dconv.hip (ops.context_train: ops.dilated_conv per unit, then the unit's own
+#: BatchNorm2d and LeakyReLU; the first unit and the heads stay stock) whenever ops.context_train_supported accepts the network
+#: and the input.  Off by default: the stock modules, bit for bit.
+CTX_TRAIN = _os.environ.get("DMC_CTX_TRAIN", "0") == "1"
 
 # ---------------------------------------------------------------------------- generators
 
@@ -148,6 +157,8 @@ class ContextNetwork(nn.Module):
     def forward(self, x):
         if CTX_EVAL and ops.context_eval_supported(self, x):
             return ops.context_eval(self, x)
+        if CTX_TRAIN and ops.context_train_supported(self, x):
+            return ops.context_train(self, x, checked=True)
         return self.conv_context(x)
 
 
@@ -168,6 +179,8 @@ class ContextNetworkAtt(nn.Module):
     def forward(self, x):
         if CTX_EVAL and ops.context_eval_supported(self, x):
             return ops.context_eval(self, x)
+        if CTX_TRAIN and ops.context_train_supported(self, x):
+            return ops.context_train(self, x, checked=True)
         x = self.conv_context(x)
         return self.predict_flow(x), self.predict_att(x)
 

@@ -2727,3 +2727,157 @@ def context_eval(net, x):
     if att is not None:
         return out_flow, out_att
     return out_flow
+
+
+# ---- ContextNetwork / ContextNetworkAtt in training: the dilated convolutions of the middle units (csrc/dconv.hip) ----
+
+def _dconv_geom_ok(x, cin, cout, dilation):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == cin and x.numel() > 0):
+        return False
+    n, _, h, w = x.shape
+    return bool(_lib.load().dmc_dconv_supported(n, h, w, cin, cout, int(dilation)))
+
+
+def _dconv_module_ok(conv):
+    if not isinstance(conv, torch.nn.Conv2d):
+        return False
+    if conv.bias is not None or conv.groups != 1 or conv.padding_mode != "zeros" or tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1):
+        return False
+    if conv.dilation[0] != conv.dilation[1] or tuple(conv.padding) != tuple(conv.dilation):
+        return False
+    return conv.weight.is_cuda and conv.weight.dtype == torch.float32
+
+
+def dilated_conv_supported(x, conv):
+    """True if ``conv(x)`` can run as ``dilated_conv(x, conv.weight, conv.dilation[0])``: a Conv2d 3x3, stride 1, padding = dilation,
+    no bias, fp32 CUDA weights (code/dmcnet/model.py:45-104, the middle units), a CUDA fp32 [N, Cin, H, W] input and a shape that
+    dmc_dconv_supported accepts (Cin, Cout in {32, 64, 96, 128}, dilation in {1, 2, 4, 8, 16}, N H W 128 < 2^31).  False on the CPU."""
+    return _dconv_module_ok(conv) and _dconv_geom_ok(x, conv.in_channels, conv.out_channels, conv.dilation[0])
+
+
+def _dconv_pack(wcl, cin, cout, transposed):
+    lib = _lib.load()
+    wp = torch.empty(lib.dmc_dconv_wpack_bytes(cin, cout), dtype=torch.uint8, device=wcl.device)
+    _lib.check(lib.dmc_dconv_pack_weights(_lib.ptr(wcl), _lib.ptr(wp), cin, cout, int(transposed), _stream()), "dmc_dconv_pack_weights")
+    return wp
+
+
+class _DilatedConv(torch.autograd.Function):
+    """Conv2d(Cin, Cout, 3, 1, d, d, bias=False) of a ContextNetwork middle unit (code/dmcnet/model.py:45-104) over channels_last
+    tensors: forward, data gradient (the same kernel on the transposed weight pack) and weight gradient on csrc/dconv.hip."""
+
+    @staticmethod
+    def forward(ctx, x, weight, dilation):
+        _need_cuda(x, weight)
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        if not (weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and _dconv_geom_ok(x, cin, cout, dilation)):
+            raise _lib.DmcHipError("dilated_conv: x %s, weight %s, dilation %s is not served by the kernels (dilated_conv_supported)"
+                                   % (tuple(x.shape), tuple(weight.shape), dilation))
+        lib = _lib.load()
+        x, wcl = _as_cl(x), _as_cl(weight.detach())
+        n, _, h, w = x.shape
+        with _span("dconv_fwd"):
+            y = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device, memory_format=_CL)
+            _lib.check(lib.dmc_dconv_fwd(_lib.ptr(x), _lib.ptr(_dconv_pack(wcl, cin, cout, False)), _lib.ptr(y), n, h, w, cin, cout, dilation,
+                                         _stream()), "dmc_dconv_fwd")
+        ctx.save_for_backward(x, weight)
+        ctx.dilation = dilation
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        lib = _lib.load()
+        d = ctx.dilation
+        n, cin, h, w = x.shape
+        cout = int(weight.shape[0])
+        dy = _as_cl(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            with _span("dconv_dgrad"):
+                wt = _dconv_pack(_as_cl(weight.detach()), cin, cout, True)
+                dx = torch.empty((n, cin, h, w), dtype=torch.float32, device=x.device, memory_format=_CL)
+                _lib.check(lib.dmc_dconv_fwd(_lib.ptr(dy), _lib.ptr(wt), _lib.ptr(dx), n, h, w, cout, cin, d, _stream()), "dmc_dconv_fwd")
+        if ctx.needs_input_grad[1]:
+            with _span("dconv_wgrad"):
+                dwcl = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device, memory_format=_CL)
+                work = torch.empty(lib.dmc_dconv_wgrad_workspace_bytes(n, h, w, cin, cout), dtype=torch.uint8, device=x.device)
+                _lib.check(lib.dmc_dconv_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dwcl), _lib.ptr(work), n, h, w, cin, cout, d, _stream()),
+                           "dmc_dconv_wgrad")
+                dw = _grad_like(dwcl, weight)
+        return dx, dw, None
+
+
+def dilated_conv(x, weight, dilation):
+    """``F.conv2d(x, weight, None, 1, dilation, dilation)`` for a 3x3 ``weight`` [Cout, Cin, 3, 3] on the kernels of csrc/dconv.hip,
+    with autograd.  ``x`` is a CUDA fp32 [N, Cin, H, W] tensor (made channels_last if it is not); the result is an ordinary
+    [N, Cout, H, W] tensor in channels_last memory.  Gradients honour ``requires_grad``: a frozen weight launches no weight
+    gradient, an input that needs none no data gradient.  Shapes: see dilated_conv_supported.  No CPU fallback."""
+    return _DilatedConv.apply(x, weight, int(dilation))
+
+
+def _ctx_train_plan(net):
+    """(first unit, [(conv, bn, act), ...] middle units, [head modules]) of a ContextNetwork / ContextNetworkAtt with BatchNorm
+    whose middle units are of the form dilated_conv serves, or None."""
+    trunk = getattr(net, "conv_context", None)
+    if not isinstance(trunk, torch.nn.Sequential):
+        return None
+    units = list(trunk)
+    if hasattr(net, "predict_att"):
+        heads = [net.predict_flow, net.predict_att]
+    else:
+        if len(units) < 3:
+            return None
+        heads = [units.pop()]
+    if len(units) < 2:
+        return None
+    middle = []
+    for u in units[1:]:
+        if not (isinstance(u, torch.nn.Sequential) and len(u) == 3 and isinstance(u[0], torch.nn.Conv2d)
+                and isinstance(u[1], torch.nn.BatchNorm2d) and isinstance(u[2], torch.nn.LeakyReLU)):
+            return None
+        middle.append((u[0], u[1], u[2]))
+    return units[0], middle, heads
+
+
+def context_train_supported(net, x):
+    """True if ``net`` (model.ContextNetwork / ContextNetworkAtt, batch_norm=True) can run its middle units' convolutions on
+    ops.dilated_conv for the input ``x``: autograd enabled, a CUDA fp32 [N, 5, H, W] input, every middle unit accepted by
+    dilated_conv_supported (a batch past the index bound therefore takes the stock route as a whole)."""
+    if not torch.is_grad_enabled():
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 5 and x.numel() > 0):
+        return False
+    plan = _ctx_train_plan(net)
+    if plan is None:
+        return False
+    first, middle, _ = plan
+    if not (isinstance(first, torch.nn.Sequential) and isinstance(first[0], torch.nn.Conv2d) and first[0].out_channels == middle[0][0].in_channels
+            and tuple(first[0].stride) == (1, 1) and tuple(first[0].kernel_size) == (3, 3) and tuple(first[0].padding) == tuple(first[0].dilation)):
+        return False
+    n, _, h, w = x.shape
+    lib = _lib.load()
+    c = first[0].out_channels
+    for conv, _, _ in middle:
+        if conv.in_channels != c or not _dconv_module_ok(conv):
+            return False
+        if not lib.dmc_dconv_supported(n, h, w, conv.in_channels, conv.out_channels, conv.dilation[0]):
+            return False
+        c = conv.out_channels
+    return True
+
+
+def context_train(net, x, checked=False):
+    """``net(x)`` of a ContextNetwork (-> gen_flow) or ContextNetworkAtt (-> (gen_flow, att_flow)) with autograd, unit by unit: the
+    first unit and the head(s) as their stock modules on a channels_last input, every middle unit as ops.dilated_conv followed by
+    the module's OWN BatchNorm2d and LeakyReLU (running statistics, momentum, num_batches_tracked and the in-place activation as
+    before).  Requires context_train_supported(net, x); ``checked=True``: the caller has just asked it (the modules' forward)."""
+    if not checked and not context_train_supported(net, x):
+        raise _lib.DmcHipError("context_train: the network or the input is not served by the kernels (context_train_supported)")
+    first, middle, heads = _ctx_train_plan(net)
+    with _span("context_train"):
+        t = first(_as_cl(x))
+        for conv, bn, act in middle:
+            t = act(bn(dilated_conv(t, conv.weight, conv.dilation[0])))
+        outs = [h(t) for h in heads]
+    return outs[0] if len(outs) == 1 else tuple(outs)

@@ -861,6 +861,35 @@ int dmc_ctx_heads_eval(const float* x, const float* w_flow, const float* stats_f
                        const float* w_att, const float* stats_att, const float* gamma_att, const float* beta_att, float* flow,
                        float* att, int N, int H, int W, dmc_stream_t stream);
 
+/* ---- ContextNetwork / ContextNetworkAtt in training: the dilated convolutions (csrc/dconv.hip) ----
+ * Replaces: Conv2d(Cin, Cout, 3, stride 1, padding d, dilation d, bias=False) of the middle units of
+ *           code/dmcnet/model.py:45-104 -- its forward, its data gradient and its weight gradient -- over NHWC fp32 tensors
+ *           (channels_last memory).  BatchNorm2d and LeakyReLU are not part of it.  bf16x3 arithmetic on the matrix cores.
+ * dmc_dconv_supported (code/dmcnet/model.py:45-104): 1 when Cin, Cout in {32, 64, 96, 128}, dilation in {1, 2, 4, 8, 16},
+ *   N, H, W > 0 and N * H * W * 128 < 2^31 (what one launch indexes), else 0.
+ * dmc_dconv_wpack_bytes (code/dmcnet/model.py:45-104): Cin * Cout * 9 * 3 * 2, the bytes of a weight pack; 0 for an
+ *   unsupported channel pair.
+ * dmc_dconv_wgrad_workspace_bytes (code/dmcnet/model.py:45-104): the bytes dmc_dconv_wgrad uses of `workspace` (per-range
+ *   partial sums, every byte written before it is read); 0 for an unsupported shape.
+ * dmc_dconv_pack_weights (code/dmcnet/model.py:45-104): w OHWI [Cout][3][3][Cin] fp32 -> wpack (three bf16 slices).
+ *   transposed == 0: the forward's pack [tap][Cin / 16][slice][Cout][16].  transposed != 0: the data gradient's,
+ *   W'[ci][t'][co] = W[co][8 - t'][ci] in the same layout with Cin and Cout exchanged, [tap'][Cout / 16][slice][Cin][16].
+ * dmc_dconv_fwd (code/dmcnet/model.py:45-104): y NHWC [N][H][W][Cout] = conv(x NHWC [N][H][W][Cin]) with the forward's pack.
+ *   The data gradient is the same call: dx = dmc_dconv_fwd(dy, transposed pack, dx, N, H, W, Cout, Cin, d) (Cin and Cout
+ *   exchanged), because with stride 1 and padding = dilation the taps mirror.
+ * dmc_dconv_wgrad (code/dmcnet/model.py:45-104): dw OHWI [Cout][3][3][Cin] = sum over pixels of dy[p][co] x[p + tap][ci],
+ *   x NHWC [N][H][W][Cin], dy NHWC [N][H][W][Cout]; every element of dw is written (a tap no pixel reaches: 0).
+ * Deterministic, no atomics; the forward / data gradient of a frame is independent of its batch.  Inputs are read only.
+ * DMC_E_INVALID before any launch (nothing written): a NULL pointer, a shape outside dmc_dconv_supported(). */
+int dmc_dconv_supported(int N, int H, int W, int Cin, int Cout, int dilation);
+size_t dmc_dconv_wpack_bytes(int Cin, int Cout);
+size_t dmc_dconv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout);
+int dmc_dconv_pack_weights(const float* w_ohwi, void* wpack, int Cin, int Cout, int transposed, dmc_stream_t stream);
+int dmc_dconv_fwd(const float* x, const void* wpack, float* y, int N, int H, int W, int Cin, int Cout, int dilation,
+                  dmc_stream_t stream);
+int dmc_dconv_wgrad(const float* x, const float* dy, float* dw_ohwi, void* workspace, int N, int H, int W, int Cin, int Cout,
+                    int dilation, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
