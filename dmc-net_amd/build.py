@@ -81,8 +81,8 @@ def build_library(force=False, verbose=False, measure=False):
             continue
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         objs.append(obj)
-        hdrs = [os.path.join(CSRC, "dmc_common.h"), os.path.join(CSRC, "x3s_common.h"), os.path.join(CSRC, "ctx_common.h"), os.path.join(CSRC, "conv_small.h"), os.path.join(CSRC, "gen_x3.h"), os.path.join(CSRC, "gen_fused.h"), os.path.join(CSRC, "gen_fused_inl.h"), os.path.join(CSRC, "gen_wgrad.h"), os.path.join(ROOT, "include", "dmcnet_hip.h"),
-                os.path.abspath(__file__)]
+        hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", "dmcnet_hip.h"),
+                                                                                                os.path.abspath(__file__)]
         if not force and os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in [path] + hdrs):
             continue                              # object newer than its source and the shared headers
         cmd = [HIPCC] + FLAGS + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, "-c", path, "-o", obj]

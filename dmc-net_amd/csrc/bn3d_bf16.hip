@@ -21,7 +21,6 @@ using namespace dmc;
 namespace {
 
 typedef unsigned short bf16_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf2f(unsigned h) { return __uint_as_float(h << 16); }
 __device__ __forceinline__ unsigned f2bf(float v) {

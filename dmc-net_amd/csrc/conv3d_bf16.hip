@@ -30,17 +30,9 @@ using namespace dmc;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;
 
 __device__ __attribute__((aligned(16))) unsigned g_zeros3d[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ void dma16(const void* src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"((unsigned long long)src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
 
 __device__ __forceinline__ unsigned f2bf(float v) {        // round to nearest even, as torch's .to(bfloat16)
     unsigned u = __float_as_uint(v);
@@ -163,12 +155,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_bf16_kernel(C3dArgs a) {
             if (IP % NW != 0 && wave + NW * j >= IP) continue;
             const bool ok = ((p_mask[j] >> tap_n) & 1) && cok;
             const unsigned long long src = ok ? p_addr[j] + (unsigned long long)toff : zeros;
-            dma16(reinterpret_cast<const void*>(src), base + (wave + NW * j) * 1024);
+            lds_dma16_off(src, base + (wave + NW * j) * 1024);
         }
 #pragma unroll
         for (int j = 0; j < NDW; ++j) {
             if (IW % NW != 0 && wave + NW * j >= IW) continue;
-            dma16(reinterpret_cast<const void*>(w_addr[j] + (unsigned long long)woff), base + PIXB + (wave + NW * j) * 1024);
+            lds_dma16_off(w_addr[j] + (unsigned long long)woff, base + PIXB + (wave + NW * j) * 1024);
         }
     };
     auto advance = [&]() {
@@ -232,8 +224,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3d_bf16_kernel(C3dArgs a) {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[kb][j]),
-                                                                        __builtin_bit_cast(bf16x8, xf[kb][i]), acc[i][j], 0, 0, 0);
+                    acc[i][j] = mfma_bf16(wf[kb][j], xf[kb][i], acc[i][j]);
         // step t + 1 must have landed: the NS - 2 steps younger than it may stay in flight while the ring is full
         C3D_LAP(1)
         if (more) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(PER_STEP * (NS - 2)) : "memory");
@@ -451,8 +442,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(C3dWgradArgs a) {
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TM; ++j)
-                        acc[t][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[i]),
-                                                                               __builtin_bit_cast(bf16x8, bf[j]), acc[t][i][j], 0, 0, 0);
+                        acc[t][i][j] = mfma_bf16(af[i], bf[j], acc[t][i][j]);
             }
             if (t + 1 < NT) {
 #pragma unroll
@@ -487,23 +477,9 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(C3dWgradArgs a) {
 // latency-bound: 15.8 us per launch on average, 56 launches per I3D micro-step.)
 __global__ __launch_bounds__(256) void conv3d_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
                                                                   int splits, int Cout, int T, int Cin) {
-    __shared__ float4 red[16][17];
     const long total = (long)Cout * T * Cin;                 // a multiple of 8 (Cin % 8 == 0)
-    const int o = threadIdx.x & 15, row = threadIdx.x >> 4;
-    for (long i0 = (long)blockIdx.x * 64; i0 < total; i0 += (long)gridDim.x * 64) {
-        const long i = i0 + 4 * o;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < total)
-            for (int k = row; k < splits; k += 16) {
-                const float4 v = *reinterpret_cast<const float4*>(part + (size_t)k * total + i);
-                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            }
-        red[row][o] = s;
-        __syncthreads();
-        if (row == 0 && i < total) {
-            float4 t = red[0][o];
-#pragma unroll
-            for (int k = 1; k < 16; ++k) { const float4 v = red[k][o]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
+    for (long i0 = (long)blockIdx.x * 64; i0 < total; i0 += (long)gridDim.x * 64)
+        wgrad_reduce_step(part, splits, total, i0, [&](long i, const float4& t) {
             const float tv[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -513,9 +489,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_reduce_kernel(const float* _
                 const int co = (int)(ie / ((long)Cin * T));
                 dw[((size_t)co * Cin + ci) * T + tt] = tv[e];
             }
-        }
-        __syncthreads();
-    }
+        });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -534,32 +508,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_reduce_kernel(const float* _
 // rows ky, three accumulators (kx) per wave.  The 64-byte halves of a pixel row are swapped when (pixel >> 1) & 1: the four
 // pixels a 16-lane group transposes then fall into different banks.  Same partial layout and reduction as above.
 // ------------------------------------------------------------------------------------------
-constexpr unsigned C3R_OOB = 0x80000000u;
-typedef const __attribute__((address_space(3))) char* c3r_lds_cptr;
-typedef short c3r_s16x4 __attribute__((ext_vector_type(4)));
-typedef float c3r_f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void c3r_dma16(const u32x4& srd, unsigned voff, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 3\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-                 :: "v"(voff), "s"(srd), "s"(lds_byte_addr) : "memory");
-}
-__device__ __forceinline__ u32x4 c3r_srd(const void* base) {
-    const unsigned long long b = (unsigned long long)base;
-    u32x4 srd;
-    srd[0] = __builtin_amdgcn_readfirstlane((unsigned)b);
-    srd[1] = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32) & 0xffffu);
-    srd[2] = 0x7fffffffu;
-    srd[3] = 0x00020000u;
-    return srd;
-}
-__device__ __forceinline__ u32x4 c3r_tr2(c3r_lds_cptr p0, c3r_lds_cptr p1) {   // eight k-values (pixels) of this lane's channel
-    const c3r_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) c3r_s16x4*)p0);
-    const c3r_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) c3r_s16x4*)p1);
-    typedef unsigned c3r_u32x2 __attribute__((ext_vector_type(2)));
-    const c3r_u32x2 ua = __builtin_bit_cast(c3r_u32x2, a), ub = __builtin_bit_cast(c3r_u32x2, b);
-    return u32x4{ua[0], ua[1], ub[0], ub[1]};
-}
-
 struct C3dRingArgs {
     const bf16_t* x;       // [N][D][H][W][Cin]
     const bf16_t* dy;      // [N][D][H][W][Cout]
@@ -602,7 +550,7 @@ __global__ __launch_bounds__(768) void conv3d_wgrad_ring_kernel(C3dRingArgs a) {
     const int HP = a.H + 2, NPL = a.N * a.D;
     const int s_begin = blockIdx.y * a.per_group;
     const int s_end = s_begin + a.per_group < a.steps ? s_begin + a.per_group : a.steps;
-    const u32x4 srd_x = c3r_srd(a.x), srd_d = c3r_srd(a.dy);
+    const u32x4 srd_x = make_srd(a.x), srd_d = make_srd(a.dy);
     // transfer lane map: pixel lane >> 3 of the instruction's 8, 16-byte piece lane & 7 of its 128-byte row
     const int tpx = lane >> 3, tpc = lane & 7;
     const int ci0 = tci * 64, co0 = tco * 64;
@@ -613,12 +561,12 @@ __global__ __launch_bounds__(768) void conv3d_wgrad_ring_kernel(C3dRingArgs a) {
         const int d = pl % a.D;
         const int c = ci0 + piece * 8;
         return (g >= 0 && pl < NPL && y >= 0 && y < a.H && x >= 0 && x < W_ && d + dz >= 0 && d + dz < a.D && c < a.Cin)
-                   ? (unsigned)(((((long)(pl + dz) * a.H + y) * W_ + x) * a.Cin + c) * 2) : C3R_OOB;
+                   ? (unsigned)(((((long)(pl + dz) * a.H + y) * W_ + x) * a.Cin + c) * 2) : OOB;
     };
     auto d_off = [&](int g, int x, int piece) -> unsigned {
         const int pl = g / HP, y = g - pl * HP - 1;
         const int c = co0 + piece * 8;
-        return (g >= 0 && pl < NPL && y >= 0 && y < a.H && c < a.Cout) ? (unsigned)(((((long)pl * a.H + y) * W_ + x) * a.Cout + c) * 2) : C3R_OOB;
+        return (g >= 0 && pl < NPL && y >= 0 && y < a.H && c < a.Cout) ? (unsigned)(((((long)pl * a.H + y) * W_ + x) * a.Cout + c) * 2) : OOB;
     };
     // input rows of group q (padded rows [R q, R q + R)) -> ring slots R (q mod NGRP) ..; instruction i by wave i % 12
     auto issue_x = [&](int q) {
@@ -631,7 +579,7 @@ __global__ __launch_bounds__(768) void conv3d_wgrad_ring_kernel(C3dRingArgs a) {
             const int piece = tpc ^ (((lpx >> 1) & 1) << 2);           // the row's 64-byte halves swapped on odd pixel pairs
             const int r = px / PW, col = px - r * PW;
             // lanes beyond the group's R x PW pixels stay out of the transfer: their LDS rows belong to the next group
-            if (px < R * PW) c3r_dma16(srd_x, x_off(R * q + r, col - 1, piece), lds0 + (unsigned)(slot0 * PW + 8 * i) * 128u);
+            if (px < R * PW) dma_buf16_soff0(srd_x, x_off(R * q + r, col - 1, piece), lds0 + (unsigned)(slot0 * PW + 8 * i) * 128u);
         }
     };
     auto issue_dy = [&](int s, int buf) {
@@ -641,11 +589,11 @@ __global__ __launch_bounds__(768) void conv3d_wgrad_ring_kernel(C3dRingArgs a) {
             const int p = 8 * i + tpx;
             const int piece = tpc ^ (((p >> 1) & 1) << 2);
             const int r = p / W_, x = p - r * W_;
-            c3r_dma16(srd_d, p < G::NPX ? d_off(R * s + r, x, piece) : C3R_OOB, lds0 + G::XBYTES + (unsigned)buf * G::DYBYTES + (unsigned)(8 * i) * 128u);
+            dma_buf16_soff0(srd_d, p < G::NPX ? d_off(R * s + r, x, piece) : OOB, lds0 + G::XBYTES + (unsigned)buf * G::DYBYTES + (unsigned)(8 * i) * 128u);
         }
     };
 
-    c3r_f32x16 acc[3];
+    f32x16 acc[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -659,7 +607,7 @@ __global__ __launch_bounds__(768) void conv3d_wgrad_ring_kernel(C3dRingArgs a) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    c3r_lds_cptr const LB = (c3r_lds_cptr)lds_r;
+    lds_cptr const LB = (lds_cptr)lds_r;
     // Loop-invariant part of the fragment addresses (round 4; 14-17 VALU instructions per MFMA before, profiles/
     // r3_pmc_i3d_kernels.csv: two modulo operations and a swizzle per unit and tap inside the step loop).  Unit (kb, u) of this
     // lane is pixel slot P = 16 kb + 8 khalf + 4 u + L / 4 of EVERY step: row r, column x and, per tap column t, the byte offset
@@ -711,12 +659,12 @@ __global__ __launch_bounds__(768) void conv3d_wgrad_ring_kernel(C3dRingArgs a) {
                 }
             }
             if (KT == 3 || trow == 1) {                              // (wave-uniform)
-                const u32x4 A = c3r_tr2(LB + dyo[0], LB + dyo[1]);
+                const u32x4 A = tr_read2(LB + dyo[0], LB + dyo[1]);
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
                     if (KT == 1 && t != 1) continue;
-                    const u32x4 B = c3r_tr2(LB + xo[0][t], LB + xo[1][t]);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), acc[t], 0, 0, 0);
+                    const u32x4 B = tr_read2(LB + xo[0][t], LB + xo[1][t]);
+                    acc[t] = mfma_bf16(A, B, acc[t]);
                 }
             }
         }
@@ -879,14 +827,8 @@ constexpr int P3_LOADERS = 4;
 constexpr int P3_THREADS = 256 + 64 * P3_LOADERS;   // waves 0 .. 3: the consumers; the rest: loaders (transfer instruction k of a plane -> loader k % P3_LOADERS)
 
 typedef __bf16 p3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float p3_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned p3_cvt2(float lo, float hi) {     // two fp32 -> packed bf16, round to nearest even (v_cvt_pk_bf16_f32)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(p3_f32x2{lo, hi}, p3_bf16x2));
-}
-
-__device__ __forceinline__ void p3_dma16(unsigned long long src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, p3_bf16x2));
 }
 
 // one consumer wave's share of a job: TMW position tiles (32 positions each) starting at tile i0 of the workgroup's P = 32 TM
@@ -957,9 +899,7 @@ __device__ __forceinline__ void p3_consume(const P3Args& a, const char* p3_lds, 
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int i = 0; i < TMW; ++i) {
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            __builtin_bit_cast(bf16x8, af[DMC_ABL(a.ablate & 32) ? 0 : tap % (PA + 1)][kb]),
-                            __builtin_bit_cast(bf16x8, bf[DMC_ABL(a.ablate & 64) ? 0 : tap % (PB + 1)][kb][i]), acc[i], 0, 0, 0);
+                        acc[i] = mfma_bf16(af[DMC_ABL(a.ablate & 32) ? 0 : tap % (PA + 1)][kb], bf[DMC_ABL(a.ablate & 64) ? 0 : tap % (PB + 1)][kb][i], acc[i]);
                         if (tap + PB < 27 && !DMC_ABL(a.ablate & 64)) ldb1(tap + PB, kb, i);
                         if (i == 0 && tap + PA < 27 && !DMC_ABL(a.ablate & 32)) lda1(tap + PA, kb);
                         __builtin_amdgcn_sched_barrier(0);
@@ -1117,7 +1057,7 @@ __global__ __launch_bounds__(P3_THREADS) void conv3d_p3_kernel(P3Args a) {
                         // consumers' 216 MFMAs -- P3_LOADERS waves share them)
 #pragma unroll
                         for (int k = 0; k < P3_MAXK; ++k)
-                            if (k < npi && k % P3_LOADERS == wave - 4) p3_dma16(zok && off[k] != 0xffffffffu ? xb + off[k] : zeros, dst + k * 960);
+                            if (k < npi && k % P3_LOADERS == wave - 4) lds_dma16_off(zok && off[k] != 0xffffffffu ? xb + off[k] : zeros, dst + k * 960);
                     }
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -35,8 +35,6 @@ using namespace dmc;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct ConvArgs {
     const float* x;        // [N][H][W][Cin]
     const float* w;        // [Cout][KH*KW][Cin]
@@ -282,13 +280,7 @@ __global__ __launch_bounds__(256) void conv_nhwc_kernel(ConvArgs a) {
 //     fragment reads -- which makes every ds_read_b128 of 16 consecutive rows conflict-free;
 //   * out-of-image taps and rows beyond M / Cout read 16 zero bytes (g_zeros).
 // ------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __attribute__((aligned(16))) float g_zeros[4] = {0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ void dma16_v(const void* src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"((unsigned long long)src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
 
 // Epilogue shared by the implicit-GEMM kernels on 32 x 32 tiles: + bias, LeakyReLU(0.2), Dropout2d keep mask, the
 // store, and the per-channel (sum, sum of squares) partials of the stored values for the BatchNorm that follows.
@@ -376,41 +368,6 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvArgs& a, f32x16 (&a
     }
 }
 
-// ---- fp32 products from bf16 matrix-core instructions ("bf16x3") -----------------------------------
-// An fp32 value is the exact sum of three bf16 values: s0 = its upper 16 bits (sign, exponent, 7 mantissa bits:
-// 8 significant bits, truncated), s1 = the upper 16 bits of the (exact) remainder, s2 = the second remainder,
-// which has at most 8 significant bits left and is therefore a bf16 value itself.  The product of two such
-// sums is formed from six of the nine slice products, (0,0) (0,1) (1,0) (0,2) (2,0) (1,1) -- each one exact in
-// the fp32 accumulator's input precision -- and the three omitted ones are below 2^-23 of |a||b|, the size of
-// one fp32 rounding of the product.  v_mfma_f32_32x32x16_bf16 retires 16 k-values per 32 cycles where
-// v_mfma_f32_32x32x2_f32 retires 2 per 64: six of them per 16 k-values are 2.67x the fp32 instruction's rate.
-// (Inf inputs become NaN, values below 2^-110 lose their low slices: neither occurs in a finite training run.)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-struct Split3 { u32x4 s[3]; };
-__device__ __forceinline__ Split3 split_bf16x3(const f32x4& lo, const f32x4& hi) {
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        u0[e] = __float_as_uint(v[e]);
-        const float r1 = v[e] - __uint_as_float(u0[e] & 0xffff0000u);
-        u1[e] = __float_as_uint(r1);
-        u2[e] = __float_as_uint(r1 - __uint_as_float(u1[e] & 0xffff0000u));
-    }
-    Split3 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {                         // (upper half of value 2e+1, upper half of value 2e)
-        r.s[0][e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
-        r.s[1][e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
-        r.s[2][e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
-    }
-    return r;
-}
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM * WN * 64) void conv2_kernel(ConvArgs a) {
     constexpr int NW = WM * WN;                            // waves: 4, or 8 (smaller wave tiles, twice the waves per SIMD)
@@ -475,10 +432,10 @@ __global__ __launch_bounds__(WM * WN * 64) void conv2_kernel(ConvArgs a) {
         if (j < NDP) {
             const bool ok = (p_mask[j < NDP ? j : 0] >> tap_n) & 1;
             const unsigned long long src = ok ? p_addr[j < NDP ? j : 0] + (unsigned long long)toff : zeros;
-            dma16_v(reinterpret_cast<const void*>(src), base + (wave + NW * j) * 1024);
+            lds_dma16_off(src, base + (wave + NW * j) * 1024);
         } else {
             const int jw = j - NDP;
-            dma16_v(reinterpret_cast<const void*>(w_addr[jw >= 0 && jw < NDW ? jw : 0] + (unsigned long long)woff),
+            lds_dma16_off(w_addr[jw >= 0 && jw < NDW ? jw : 0] + (unsigned long long)woff,
                     base + BM * 128 + (wave + NW * jw) * 1024);
         }
     };
@@ -570,7 +527,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv2_kernel(ConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Third generation: the same implicit GEMM in bf16x3 arithmetic (above) for Cin % 32 == 0, Cout % 64 == 0.
+// Third generation: the same implicit GEMM in bf16x3 arithmetic (mma_bf16.h) for Cin % 32 == 0, Cout % 64 == 0.
 //   * weights arrive already split (conv_split_w_kernel: three bf16 slices [3][Cout][KK][Cin], a few microseconds per
 //     call), so only the activation fragments are split in registers (11 VALU instructions per pair of values,
 //     overlapped with the matrix pipe); activations stay fp32 in HBM and LDS: nothing upstream changes;
@@ -650,12 +607,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3_kernel(ConvArgs a) {
         for (int j = 0; j < NDP; ++j) {
             const bool ok = (p_mask[j] >> tap_n) & 1;
             const unsigned long long src = ok ? p_addr[j] + (unsigned long long)toff : zeros;
-            dma16_v(reinterpret_cast<const void*>(src), base + (wave + NW * j) * 1024);
+            lds_dma16_off(src, base + (wave + NW * j) * 1024);
         }
 #pragma unroll
         for (int j = 0; j < NDW; ++j)
             if (WD % NW == 0 || wave + NW * j < WD)
-                dma16_v(reinterpret_cast<const void*>(w_addr[j] + (unsigned long long)woff), base + PIXB + (wave + NW * j) * 1024);
+                lds_dma16_off(w_addr[j] + (unsigned long long)woff, base + PIXB + (wave + NW * j) * 1024);
     };
 
     f32x16 acc[TM][TN];
@@ -707,7 +664,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv3_kernel(ConvArgs a) {
                 xs[i].s[0] = __builtin_bit_cast(u32x4, r.lo[i]); xs[i].s[1] = __builtin_bit_cast(u32x4, r.hi[i]);
                 xs[i].s[2] = __builtin_bit_cast(u32x4, r.lo[i]);
             } else {
-                xs[i] = split_bf16x3(r.lo[i], r.hi[i]);
+                xs[i] = split8(r.lo[i], r.hi[i]);
             }
         }
     };
@@ -809,13 +766,11 @@ __global__ __launch_bounds__(256) void conv_split_w_kernel(const float* __restri
         } else {
             v = w[i];
         }
-        const unsigned u0 = __float_as_uint(v);
-        const float r1 = v - __uint_as_float(u0 & 0xffff0000u);
-        const unsigned u1 = __float_as_uint(r1);
-        const unsigned u2 = __float_as_uint(r1 - __uint_as_float(u1 & 0xffff0000u));
-        ws[i] = (unsigned short)(u0 >> 16);
-        ws[total + i] = (unsigned short)(u1 >> 16);
-        ws[2 * total + i] = (unsigned short)(u2 >> 16);
+        unsigned s0, s1, s2;
+        split3_bf16(v, s0, s1, s2);
+        ws[i] = (unsigned short)s0;
+        ws[total + i] = (unsigned short)s1;
+        ws[2 * total + i] = (unsigned short)s2;
     }
 }
 
@@ -833,13 +788,11 @@ __global__ __launch_bounds__(256) void conv_split_w2_kernel(const float* __restr
         } else {
             v = w[i];
         }
-        const unsigned u0 = __float_as_uint(v);
-        const float r1 = v - __uint_as_float(u0 & 0xffff0000u);
-        const unsigned u1 = __float_as_uint(r1);
-        const unsigned u2 = __float_as_uint(r1 - __uint_as_float(u1 & 0xffff0000u));
-        ws[i] = (unsigned short)(u0 >> 16);
-        ws[total + i] = (unsigned short)(u1 >> 16);
-        ws[2 * total + i] = (unsigned short)(u2 >> 16);
+        unsigned s0, s1, s2;
+        split3_bf16(v, s0, s1, s2);
+        ws[i] = (unsigned short)s0;
+        ws[total + i] = (unsigned short)s1;
+        ws[2 * total + i] = (unsigned short)s2;
     }
 }
 
@@ -1012,26 +965,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradConvArgs a) {
 // order, then the 16 lanes are combined in order through LDS): fixed summation order, numel / 64 workgroups
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
                                                                 int nslice, long numel) {
-    __shared__ float4 red[16][17];
-    const int o = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    for (long i0 = (long)blockIdx.x * 64; i0 < numel; i0 += (long)gridDim.x * 64) {
-        const long i = i0 + 4 * o;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < numel)
-            for (int k = sl; k < nslice; k += 16) {
-                const float4 v = *reinterpret_cast<const float4*>(part + (size_t)k * numel + i);
-                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            }
-        red[sl][o] = s;
-        __syncthreads();
-        if (sl == 0 && i < numel) {
-            float4 t = red[0][o];
-#pragma unroll
-            for (int k = 1; k < 16; ++k) { const float4 v = red[k][o]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-            *reinterpret_cast<float4*>(dw + i) = t;
-        }
-        __syncthreads();
-    }
+    for (long i0 = (long)blockIdx.x * 64; i0 < numel; i0 += (long)gridDim.x * 64) wgrad_reduce_step(part, dw, nslice, numel, i0);
 }
 
 
@@ -1246,13 +1180,13 @@ __global__ __launch_bounds__(Wg2<KS>::WAVES * 64) void conv_wgrad2_kernel(Wgrad2
         if (d < dy_dma) {                                           // wave-uniform
             const int p = 4 * d + sub;
             const bool ok = p < a.P && p < prem;
-            dma16_v(ok ? dyb + (long)p * a.Cout * 4 : zeros, ibase + d * 1024);
+            lds_dma16_off(ok ? dyb + (long)p * a.Cout * 4 : zeros, ibase + d * 1024);
         } else {
             const int pp = 4 * (d - dy_dma) + sub;
             const int pr = (int)(((unsigned long long)pp * a.inv_xc) >> 32), pc = pp - pr * a.XC;
             const int iy = iy0 + pr, ix = pc - PAD;
             const bool ok = pp < x_rows && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            dma16_v(ok ? xb + ((long)iy * a.W + ix) * a.Cin * 4 : zeros, ibase + d * 1024);
+            lds_dma16_off(ok ? xb + ((long)iy * a.W + ix) * a.Cin * 4 : zeros, ibase + d * 1024);
         }
     };
 
@@ -1478,13 +1412,13 @@ __global__ __launch_bounds__(768) void conv_wgrad3_kernel(Wgrad3Args a) {
             const int p = 4 * d + sub;
             const int r = (int)(((unsigned long long)p * a.inv_owp) >> 32), c = p - r * a.OWp;
             const bool ok = r < rows_left && c < a.OW;
-            dma16_v(ok ? dyb + ((long)r * a.OW + c) * a.Cout * 4 : zeros, ibase + d * 1024);
+            lds_dma16_off(ok ? dyb + ((long)r * a.OW + c) * a.Cout * 4 : zeros, ibase + d * 1024);
         } else {
             const int pp = 4 * (d - dy_dma) + sub;
             const int pr = (int)(((unsigned long long)pp * a.inv_xc) >> 32), pc = pp - pr * a.XC;
             const int iy = iy0 + pr, ix = pc - 1;
             const bool ok = pp < x_rows && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            dma16_v(ok ? xb + ((long)iy * a.W + ix) * a.Cin * 4 : zeros, ibase + d * 1024);
+            lds_dma16_off(ok ? xb + ((long)iy * a.W + ix) * a.Cin * 4 : zeros, ibase + d * 1024);
         }
     };
 
@@ -1528,34 +1462,24 @@ __global__ __launch_bounds__(768) void conv_wgrad3_kernel(Wgrad3Args a) {
         auto process = [&](const Raw& w) {
             unsigned a0[8], a1[8], a2[8], b0[NRAW], b1[NRAW], b2[NRAW];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                a0[j] = __float_as_uint(w.d[j]);
-                const float r1 = w.d[j] - __uint_as_float(a0[j] & 0xffff0000u);
-                a1[j] = __float_as_uint(r1);
-                a2[j] = __float_as_uint(r1 - __uint_as_float(a1[j] & 0xffff0000u));
-            }
+            for (int j = 0; j < 8; ++j) split3(w.d[j], a0[j], a1[j], a2[j]);
 #pragma unroll
-            for (int j = 0; j < NRAW; ++j) {
-                b0[j] = __float_as_uint(w.x[j]);
-                const float r1 = w.x[j] - __uint_as_float(b0[j] & 0xffff0000u);
-                b1[j] = __float_as_uint(r1);
-                b2[j] = __float_as_uint(r1 - __uint_as_float(b1[j] & 0xffff0000u));
-            }
+            for (int j = 0; j < NRAW; ++j) split3(w.x[j], b0[j], b1[j], b2[j]);
             u32x4 A0, A1, A2;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                A0[e] = __builtin_amdgcn_perm(a0[2 * e + 1], a0[2 * e], 0x07060302u);
-                A1[e] = __builtin_amdgcn_perm(a1[2 * e + 1], a1[2 * e], 0x07060302u);
-                A2[e] = __builtin_amdgcn_perm(a2[2 * e + 1], a2[2 * e], 0x07060302u);
+                A0[e] = pack_hi(a0[2 * e + 1], a0[2 * e]);
+                A1[e] = pack_hi(a1[2 * e + 1], a1[2 * e]);
+                A2[e] = pack_hi(a2[2 * e + 1], a2[2 * e]);
             }
 #pragma unroll
             for (int t = 0; t < 3; ++t) {                           // horizontal tap t: pixel j reads patch value j s + t
                 u32x4 B0, B1, B2;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    B0[e] = __builtin_amdgcn_perm(b0[(2 * e + 1) * STRIDE + t], b0[2 * e * STRIDE + t], 0x07060302u);
-                    B1[e] = __builtin_amdgcn_perm(b1[(2 * e + 1) * STRIDE + t], b1[2 * e * STRIDE + t], 0x07060302u);
-                    B2[e] = __builtin_amdgcn_perm(b2[(2 * e + 1) * STRIDE + t], b2[2 * e * STRIDE + t], 0x07060302u);
+                    B0[e] = pack_hi(b0[(2 * e + 1) * STRIDE + t], b0[2 * e * STRIDE + t]);
+                    B1[e] = pack_hi(b1[(2 * e + 1) * STRIDE + t], b1[2 * e * STRIDE + t]);
+                    B2[e] = pack_hi(b2[(2 * e + 1) * STRIDE + t], b2[2 * e * STRIDE + t]);
                 }
                 acc[t] = mfma_bf16(A0, B2, acc[t]);
                 acc[t] = mfma_bf16(A2, B0, acc[t]);

@@ -4,7 +4,7 @@
 // on 56 x 56 maps, code/dmcnet_GAN/model.py:254-279 as chained in Discriminator3, :332-366 -- at 240 / 120 frames per step:
 // 386 / 193 MB of activations per launch against 13.9 GFLOP.  On the fp32 matrix cores (v_mfma_f32_16x16x4_f32, K = 144:
 // conv_nhwc_kernel / conv2_kernel) they sit at the fp32-MFMA roof (0.36 ms for a 240-frame block: 0.49 of 157 TFLOP/s); in
-// bf16x3 arithmetic (conv_nhwc.hip: an fp32 value = the exact sum of three bf16 slices, six slice products per product
+// bf16x3 arithmetic (mma_bf16.h: an fp32 value = the exact sum of three bf16 slices, six slice products per product
 // block, fp32 accumulate: fp32-level error) the matrix work shrinks 2.67x and the layers become HBM streams.
 //
 // v_mfma_f32_16x16x32_bf16: rows = the 16 output channels of a row tile, columns = 16 consecutive output pixels of an image row,
@@ -18,11 +18,9 @@
 // squares) of the result in fp64 for the BatchNorm that follows, 16-byte stores (a wave writes 1 KB of consecutive memory).
 // The data gradient is the same kernel on dy with the weights packed transposed and mirrored.
 #include "dmc_common.h"
-#include "x3s_common.h"
 #include "conv_small.h"
 
 using namespace dmc;
-using namespace dmc::x3;
 
 namespace {
 
@@ -261,14 +259,14 @@ __global__ __launch_bounds__(256) void csm_pack_s2_kernel(const float* __restric
         const int tap = 2 * kb + (kk >> 4), ci = kk & 15, co = mt * 16 + row;
         float v = 0.f;
         if (tap < 9) v = w[((size_t)co * 9 + tap) * Csm2::CIN + ci];
-        unsigned u0, u1, u2;
-        split3(v, u0, u1, u2);
+        unsigned s0, s1, s2;
+        split3_bf16(v, s0, s1, s2);
         const size_t e = (size_t)((kk >> 3) * 16 + row) * 8 + (kk & 7);
         const size_t f = (size_t)(kb * Csm2::MT + mt) * 512;
         const size_t sl = (size_t)Csm2::KB * Csm2::MT * 512;
-        wp[f + e] = (unsigned short)(u0 >> 16);
-        wp[sl + f + e] = (unsigned short)(u1 >> 16);
-        wp[2 * sl + f + e] = (unsigned short)(u2 >> 16);
+        wp[f + e] = (unsigned short)s0;
+        wp[sl + f + e] = (unsigned short)s1;
+        wp[2 * sl + f + e] = (unsigned short)s2;
     }
 }
 
@@ -469,12 +467,12 @@ __global__ __launch_bounds__(256) void csm_pack_d2_kernel(const float* __restric
     if (i >= 9 * 16 * 32) return;
     const int kk = i & 31, row = (i >> 5) & 15, j = i >> 9;
     const float v = w[((size_t)kk * 9 + CSM2D_TAP[j]) * 16 + row];
-    unsigned u0, u1, u2;
-    split3(v, u0, u1, u2);
+    unsigned s0, s1, s2;
+    split3_bf16(v, s0, s1, s2);
     const size_t e = (size_t)((kk >> 3) * 16 + row) * 8 + (kk & 7), f = (size_t)j * 512, sl = (size_t)9 * 512;
-    wp[f + e] = (unsigned short)(u0 >> 16);
-    wp[sl + f + e] = (unsigned short)(u1 >> 16);
-    wp[2 * sl + f + e] = (unsigned short)(u2 >> 16);
+    wp[f + e] = (unsigned short)s0;
+    wp[sl + f + e] = (unsigned short)s1;
+    wp[2 * sl + f + e] = (unsigned short)s2;
 }
 
 struct Csm2dArgs {
@@ -600,7 +598,7 @@ __global__ __launch_bounds__(256) void csm_dgrad_s2_kernel(Csm2dArgs a) {
 // 0, 1 -> tile a, 2, 3 -> tile b).  Per tile pair a wave loads the two 3 x 18-pixel neighbourhoods of x and the two 16-pixel
 // segments of g (range-checked buffer loads: zeros outside the image / beyond the row), splits every 8-channel piece once
 // and parks the slices PIXEL-MAJOR in its mini patch in LDS ([slice][chunk of 16 channels][pixel][16 channels]): both MFMA
-// operands then need "eight consecutive pixels of one channel per lane" -- ds_read_b64_tr_b16 (x3s_common.h) transposes
+// operands then need "eight consecutive pixels of one channel per lane" -- ds_read_b64_tr_b16 (tr_read2, mma_bf16.h) transposes
 // on the way out of LDS, the nine taps are nine pixel offsets into the same patch.  The 9 x (C/16)^2 accumulator tiles
 // stay in registers for the whole launch; partials per workgroup (waves summed in fixed order) and a fixed-order reduction
 // over the workgroups: deterministic, no atomics.  (conv_wgrad_small_kernel, fp32 MFMA: 0.25-0.28 ms per launch at 240 / 120
@@ -724,7 +722,7 @@ __global__ __launch_bounds__(256, C == 16 ? 3 : 1) void csm_wgrad_kernel(CsmWgAr
             for (int i = 0; i < MT; ++i)
 #pragma unroll
                 for (int sl = 0; sl < 3; ++sl)
-                    tr_read2(LB + g_off + sl * GS + i * GPL, LB + g_off + sl * GS + i * GPL + 4 * 32, A[i][sl]);
+                    A[i][sl] = tr_read2(LB + g_off + sl * GS + i * GPL, LB + g_off + sl * GS + i * GPL + 4 * 32);
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int toff = ((t / 3) * 18 + (t % 3)) * 32;                // patch row dy, column dx of the tap
@@ -733,7 +731,7 @@ __global__ __launch_bounds__(256, C == 16 ? 3 : 1) void csm_wgrad_kernel(CsmWgAr
                     u32x4 B[3];
 #pragma unroll
                     for (int sl = 0; sl < 3; ++sl)
-                        tr_read2(LB + x_off + toff + sl * XS + j * XPL, LB + x_off + toff + sl * XS + j * XPL + 4 * 32, B[sl]);
+                        B[sl] = tr_read2(LB + x_off + toff + sl * XS + j * XPL, LB + x_off + toff + sl * XS + j * XPL + 4 * 32);
 #pragma unroll
                     for (int i = 0; i < MT; ++i) {
                         acc[t][i][j] = mfma16(A[i][0], B[2], acc[t][i][j]);
@@ -913,7 +911,7 @@ __global__ __launch_bounds__(CIN == 32 ? 512 : 256) void csm_wgrad_s2_kernel(Csm
     f32x4 acc[NACC];
 #pragma unroll
     for (int i = 0; i < NACC; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // transposing reads (x3s_common.h): lane (L, kq) hands in pixel 8 (kq & 1) + L / 4 (+ 4) of tile kq >> 1, channels 4 (L % 4) ..
+    // transposing reads (tr_read2, mma_bf16.h): lane (L, kq) hands in pixel 8 (kq & 1) + L / 4 (+ 4) of tile kq >> 1, channels 4 (L % 4) ..
     const int trb = (L & 3) * 8 + (8 * (kq & 1) + (L >> 2)) * 32;
     const int g_off = 3 * XS + cot * GPL + (kq >> 1) * 16 * 32 + trb;
     const int x_off = cit * XPL + (kq >> 1) * 99 * 32 + trb;
@@ -934,13 +932,13 @@ __global__ __launch_bounds__(CIN == 32 ? 512 : 256) void csm_wgrad_s2_kernel(Csm
         lds_cptr const LB = (lds_cptr)lds[it & 1];
         u32x4 A[3];
 #pragma unroll
-        for (int sl = 0; sl < 3; ++sl) tr_read2(LB + g_off + sl * GS, LB + g_off + sl * GS + 4 * 32, A[sl]);
+        for (int sl = 0; sl < 3; ++sl) A[sl] = tr_read2(LB + g_off + sl * GS, LB + g_off + sl * GS + 4 * 32);
 #pragma unroll
         for (int i = 0; i < NACC; ++i) {
             if (i >= nt) break;                                 // (wave-uniform)
             u32x4 B[3];
 #pragma unroll
-            for (int sl = 0; sl < 3; ++sl) tr_read2(LB + x_off + toff[i] + sl * XS, LB + x_off + toff[i] + sl * XS + 4 * 32, B[sl]);
+            for (int sl = 0; sl < 3; ++sl) B[sl] = tr_read2(LB + x_off + toff[i] + sl * XS, LB + x_off + toff[i] + sl * XS + 4 * 32);
             acc[i] = mfma16(A[0], B[2], acc[i]);
             acc[i] = mfma16(A[2], B[0], acc[i]);
             acc[i] = mfma16(A[1], B[1], acc[i]);
@@ -979,15 +977,15 @@ __global__ __launch_bounds__(256) void csm_pack_kernel(const float* __restrict__
         const int r = mt * 16 + row;                                // result channel of this direction
         float v = 0.f;
         if (tap < 9) v = transposed ? w[((size_t)kc * 9 + (8 - tap)) * C + r] : w[((size_t)r * 9 + tap) * C + kc];
-        unsigned u0, u1, u2;
-        split3(v, u0, u1, u2);
+        unsigned s0, s1, s2;
+        split3_bf16(v, s0, s1, s2);
         // fragment (slice, kb, mt): lane (row, kq = kk / 8) holds eight k-values: element index within the fragment
         const size_t e = (size_t)((kk >> 3) * 16 + row) * 8 + (kk & 7);
         const size_t f = (size_t)(kb * G::MT + mt) * 512;
         const size_t sl = (size_t)G::KB * G::MT * 512;
-        wp[f + e] = (unsigned short)(u0 >> 16);
-        wp[sl + f + e] = (unsigned short)(u1 >> 16);
-        wp[2 * sl + f + e] = (unsigned short)(u2 >> 16);
+        wp[f + e] = (unsigned short)s0;
+        wp[sl + f + e] = (unsigned short)s1;
+        wp[2 * sl + f + e] = (unsigned short)s2;
     }
 }
 

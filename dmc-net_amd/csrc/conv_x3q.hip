@@ -439,12 +439,12 @@ __global__ __launch_bounds__(256) void x3q_pack_w_kernel(const float* __restrict
         const int tap = transposed ? slot : FWD_TAP[slot];
         const int co = transposed ? k : r, ci = transposed ? r : k;
         const float v = tap < 9 ? w3[((long)co * 9 + tap) * Cin + ci] : w1[(long)co * Cin + ci];
-        unsigned u0, u1, u2;
-        split3(v, u0, u1, u2);
+        unsigned s0, s1, s2;
+        split3_bf16(v, s0, s1, s2);
         const size_t base = ((((size_t)(rt * nchunk + ch) * 10 + slot) * 3) * 64 + rl) * 16 + (kk ^ (((rl >> 3) & 1) << 3));
-        dst[base] = (unsigned short)(u0 >> 16);
-        dst[base + 64 * 16] = (unsigned short)(u1 >> 16);
-        dst[base + 2 * 64 * 16] = (unsigned short)(u2 >> 16);
+        dst[base] = (unsigned short)s0;
+        dst[base + 64 * 16] = (unsigned short)s1;
+        dst[base + 2 * 64 * 16] = (unsigned short)s2;
     }
 }
 
@@ -738,10 +738,10 @@ __global__ __launch_bounds__(768) void x3q_wgrad_kernel(X3qWgArgs a) {
             u32x4 A[3], B[3][3];
 #pragma unroll
             for (int sl = 0; sl < 3; ++sl) {
-                tr_read2(LB + dyo[0] + sl * 4 * DYPL * 32, LB + dyo[1] + sl * 4 * DYPL * 32, A[sl]);
-                tr_read2(LB + xa[0] + sl * G::SLB, LB + xa[1] + sl * G::SLB, B[0][sl]);
-                tr_read2(LB + xb[0] + sl * G::SLB + 32, LB + xb[1] + sl * G::SLB + 32, B[1][sl]);
-                tr_read2(LB + xa[0] + sl * G::SLB + 32, LB + xa[1] + sl * G::SLB + 32, B[2][sl]);
+                A[sl] = tr_read2(LB + dyo[0] + sl * 4 * DYPL * 32, LB + dyo[1] + sl * 4 * DYPL * 32);
+                B[0][sl] = tr_read2(LB + xa[0] + sl * G::SLB, LB + xa[1] + sl * G::SLB);
+                B[1][sl] = tr_read2(LB + xb[0] + sl * G::SLB + 32, LB + xb[1] + sl * G::SLB + 32);
+                B[2][sl] = tr_read2(LB + xa[0] + sl * G::SLB + 32, LB + xa[1] + sl * G::SLB + 32);
             }
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
@@ -827,8 +827,8 @@ __global__ __launch_bounds__(256) void x3q_wgrad1_kernel(X3qWg1Args a) {
             const int P0 = 16 * kb + 8 * khalf + (L >> 2), P1 = P0 + 4;
 #pragma unroll
             for (int sl = 0; sl < 3; ++sl) {
-                tr_read2(LB + db + sl * 4 * W1PL * 32 + P0 * 32, LB + db + sl * 4 * W1PL * 32 + P1 * 32, A[sl]);
-                tr_read2(LB + xb + sl * 4 * W1PL * 32 + P0 * 32, LB + xb + sl * 4 * W1PL * 32 + P1 * 32, B[sl]);
+                A[sl] = tr_read2(LB + db + sl * 4 * W1PL * 32 + P0 * 32, LB + db + sl * 4 * W1PL * 32 + P1 * 32);
+                B[sl] = tr_read2(LB + xb + sl * 4 * W1PL * 32 + P0 * 32, LB + xb + sl * 4 * W1PL * 32 + P1 * 32);
             }
             acc = mfma_bf16(A[0], B[2], acc);
             acc = mfma_bf16(A[2], B[0], acc);
@@ -851,26 +851,7 @@ __global__ __launch_bounds__(256) void x3q_wgrad1_kernel(X3qWg1Args a) {
 
 // dw = sum over groups of the partials, fixed order (16 group lanes x 16 float4 columns per workgroup)
 __global__ __launch_bounds__(256) void x3q_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int ngroup, long numel) {
-    __shared__ float4 red[16][17];
-    const int o = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    for (long i0 = (long)blockIdx.x * 64; i0 < numel; i0 += (long)gridDim.x * 64) {
-        const long i = i0 + 4 * o;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < numel)
-            for (int k = sl; k < ngroup; k += 16) {
-                const float4 v = *reinterpret_cast<const float4*>(part + (size_t)k * numel + i);
-                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-            }
-        red[sl][o] = s;
-        __syncthreads();
-        if (sl == 0 && i < numel) {
-            float4 t = red[0][o];
-#pragma unroll
-            for (int k = 1; k < 16; ++k) { const float4 v = red[k][o]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-            *reinterpret_cast<float4*>(dw + i) = t;
-        }
-        __syncthreads();
-    }
+    for (long i0 = (long)blockIdx.x * 64; i0 < numel; i0 += (long)gridDim.x * 64) wgrad_reduce_step(part, dw, ngroup, numel, i0);
 }
 
 struct QWgPlan { int R, HP, steps, tiles, groups, per_group, steps1, groups1, per_group1; };

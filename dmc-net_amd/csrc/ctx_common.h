@@ -10,36 +10,11 @@
 namespace dmc {
 namespace ctxk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct GatherArgs {
     const float* x;                 // [N][H][W][Cin]
     const unsigned short* wpack;    // [9][Cin / 16][3][Cout][16] bf16
     int N, H, W, Cin, d, M;         // M = N H W
 };
-
-// the three bf16 slices (truncating split, as conv_nhwc.hip's split_bf16x3) of 8 consecutive values
-struct Split3 { u32x4 s[3]; };
-__device__ __forceinline__ Split3 split3(const f32x4& lo, const f32x4& hi) {
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x3s_split3(v[e], u0[e], u1[e], u2[e]);
-    Split3 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        r.s[0][e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
-        r.s[1][e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
-        r.s[2][e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
-    }
-    return r;
-}
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 template <int TN>
 struct GatherLds {
@@ -133,7 +108,7 @@ __device__ __forceinline__ int gather_gemm(const GatherArgs& a, char* lds, f32x1
         const int buf = s & 1;
         Split3 xs[TM];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) xs[i] = split3(xlo[i], xhi[i]);
+        for (int i = 0; i < TM; ++i) xs[i] = split8(xlo[i], xhi[i]);
         if (s + 1 < nsteps) load_step(s + 1);              // in flight during the MFMAs below
         const char* wb = lds + buf * CH + foff;
         // the six slice products, grouped by weight slice: (0,2) (0,1) (0,0) | (1,1) (1,0) | (2,0)
@@ -166,14 +141,14 @@ static __global__ __launch_bounds__(256) void pack_kernel(const float* __restric
     const int nkb = K >> 4;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
         const int ci = i % Cin, tap = (i / Cin) % 9, co = i / (9 * Cin);
-        unsigned u0, u1, u2;
-        x3s_split3(w[i], u0, u1, u2);
+        unsigned s0, s1, s2;
+        split3_bf16(w[i], s0, s1, s2);
         const int t = transposed ? 8 - tap : tap, k = transposed ? co : ci, r = transposed ? ci : co;
         const long panel = ((long)(t * nkb + (k >> 4)) * 3) * R;            // in rows of 16
         const long o = (panel + r) * 16 + (k & 15);
-        wp[o] = (unsigned short)(u0 >> 16);
-        wp[o + (long)R * 16] = (unsigned short)(u1 >> 16);
-        wp[o + (long)R * 32] = (unsigned short)(u2 >> 16);
+        wp[o] = (unsigned short)s0;
+        wp[o + (long)R * 16] = (unsigned short)s1;
+        wp[o + (long)R * 32] = (unsigned short)s2;
     }
 }
 

@@ -26,7 +26,6 @@
 // No atomics anywhere: results are bit-identical from run to run.  All tensor offsets are 64-bit; dmc_dconv_supported bounds
 // N H W 128 below 2^31 so that pixel indices fit an int.
 #include "ctx_common.h"
-#include "x3s_common.h"
 
 using namespace dmc;
 using namespace dmc::ctxk;
@@ -144,13 +143,13 @@ __global__ __launch_bounds__(256) void dconv_wgrad_kernel(WgArgs a) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             if (dlive[r]) {
-                const Split3 s3 = split3(dlo[r], dhi[r]);
+                const Split3 s3 = split8(dlo[r], dhi[r]);
                 char* q = lds + (dcg[r] >> 1) * PLANE + dpix[r] * 32 + (dcg[r] & 1) * 16;
 #pragma unroll
                 for (int sl = 0; sl < 3; ++sl) *reinterpret_cast<u32x4*>(q + sl * NCHUNK * PLANE) = s3.s[sl];
             }
             if (xlive[r]) {
-                const Split3 s3 = split3(xlo[r], xhi[r]);
+                const Split3 s3 = split8(xlo[r], xhi[r]);
                 char* q = lds + TILE_BYTES + (xcg[r] >> 1) * PLANE + xpix[r] * 32 + (xcg[r] & 1) * 16;
 #pragma unroll
                 for (int sl = 0; sl < 3; ++sl) *reinterpret_cast<u32x4*>(q + sl * NCHUNK * PLANE) = s3.s[sl];
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(256) void dconv_wgrad_kernel(WgArgs a) {
 
     // fragment address of this lane inside a 32-channel tile's pair of planes: unit (kb, u) is pixel 16 kb + 8 khalf + 4 u + L / 4
     const int frag = grp * PLANE + (8 * khalf + (L >> 2)) * 32 + (L & 3) * 8;
-    x3::lds_cptr const LB = (x3::lds_cptr)lds;
+    lds_cptr const LB = (lds_cptr)lds;
 
     if (s_begin < s_end) {
         load_step(s_begin);
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(256) void dconv_wgrad_kernel(WgArgs a) {
 #pragma unroll
         for (int kb = 0; kb < KP / 16; ++kb) {
             int have_a = -1, have_b = -1;
-            x3::u32x4 A[3], B[3];
+            u32x4 A[3], B[3];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int q = wave + 4 * j;
@@ -191,21 +190,21 @@ __global__ __launch_bounds__(256) void dconv_wgrad_kernel(WgArgs a) {
                     have_a = tco;
                     const int o = frag + 2 * tco * PLANE + kb * 16 * 32;
 #pragma unroll
-                    for (int sl = 0; sl < 3; ++sl) x3::tr_read2(LB + o + sl * NCHUNK * PLANE, LB + o + sl * NCHUNK * PLANE + 4 * 32, A[sl]);
+                    for (int sl = 0; sl < 3; ++sl) A[sl] = tr_read2(LB + o + sl * NCHUNK * PLANE, LB + o + sl * NCHUNK * PLANE + 4 * 32);
                 }
                 if (tci != have_b) {
                     have_b = tci;
                     const int o = TILE_BYTES + frag + 2 * tci * PLANE + kb * 16 * 32;
 #pragma unroll
-                    for (int sl = 0; sl < 3; ++sl) x3::tr_read2(LB + o + sl * NCHUNK * PLANE, LB + o + sl * NCHUNK * PLANE + 4 * 32, B[sl]);
+                    for (int sl = 0; sl < 3; ++sl) B[sl] = tr_read2(LB + o + sl * NCHUNK * PLANE, LB + o + sl * NCHUNK * PLANE + 4 * 32);
                 }
                 // the six slice products, the smallest first (the order of x3s_wgrad_kernel)
-                acc[j] = x3::mfma_bf16(A[0], B[2], acc[j]);
-                acc[j] = x3::mfma_bf16(A[2], B[0], acc[j]);
-                acc[j] = x3::mfma_bf16(A[1], B[1], acc[j]);
-                acc[j] = x3::mfma_bf16(A[0], B[1], acc[j]);
-                acc[j] = x3::mfma_bf16(A[1], B[0], acc[j]);
-                acc[j] = x3::mfma_bf16(A[0], B[0], acc[j]);
+                acc[j] = mfma_bf16(A[0], B[2], acc[j]);
+                acc[j] = mfma_bf16(A[2], B[0], acc[j]);
+                acc[j] = mfma_bf16(A[1], B[1], acc[j]);
+                acc[j] = mfma_bf16(A[0], B[1], acc[j]);
+                acc[j] = mfma_bf16(A[1], B[0], acc[j]);
+                acc[j] = mfma_bf16(A[0], B[0], acc[j]);
             }
         }
         __syncthreads();                                   // every wave has read the step's tiles

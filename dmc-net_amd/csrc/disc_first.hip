@@ -174,7 +174,6 @@ __global__ __launch_bounds__(256) void disc_first_dgrad_kernel(const float* __re
 // coordinates advance incrementally (no divisions in the loop).  Partials [wave][2][16 x 16] are summed
 // in fixed order in fp64 by the final kernel: deterministic.
 constexpr int FW_WAVES = 2048;                 // 256 CUs x 8 waves
-typedef float fw_f32x4 __attribute__((ext_vector_type(4)));
 
 template <int COUT>
 __global__ __launch_bounds__(256) void disc_first_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g,
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(256) void disc_first_wgrad_kernel(const float* __re
     const int ky1 = 1, kx1 = (i16 == 0) ? 0 : 1;            // taps 7 = (2, 1), 8 = (2, 2) -> offsets (+1, 0), (+1, +1)
     const bool t1_tap = i16 < 2, t1_one = i16 == 2;
     const bool co_ok = i16 < COUT;
-    fw_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     // this lane's pixel of the current quad
     long p = 4 * q0 + kq;
     int n = 0, oy = 0, ox = 0;

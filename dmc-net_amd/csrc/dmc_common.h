@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "dmcnet_hip.h"
+#include "mma_bf16.h"
 
 namespace dmc {
 
@@ -148,20 +149,6 @@ struct GradPtrs {
 
 }  // namespace dmc
 
-// ---- LDS-DMA helpers shared by kernels outside gen_tiny.hip -----------------------------------
-// global_load_lds_dwordx4 through inline assembly (the compiler then inserts no vmcnt(0) in front
-// of unrelated ds_reads; completion is tracked by hand with s_waitcnt vmcnt).  Address = 64-bit
-// scalar base + 32-bit per-lane byte offset; the LDS destination is lds_byte_addr + 16 * lane.
-namespace dmc {
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(size_t)(lds_ptr_t)p; }
-__device__ __forceinline__ void lds_dma16(unsigned long long sbase, unsigned voff, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :: "v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
-}  // namespace dmc
-
 // ---- lane sums on the VALU's data-parallel primitives (DPP) -----------------------------------------------
 // A butterfly of __shfl_xor is one ds_bpermute_b32 per dword and level -- an LDS-crossbar round trip each, waited for: the fp64
 // BatchNorm sums of an accumulator tile (32 values x 5 levels x 2 dwords) cost more than a short convolution's main loop.
@@ -212,50 +199,24 @@ __device__ __forceinline__ void bn_eval_affine(const BnEval& b, int C, int c, fl
 // An fp32 value is the exact sum of three bf16 values: s0 = its upper 16 bits, s1 = the upper 16 bits of the exact
 // remainder, s2 = the second remainder.  A slice tensor of a [M][C] fp32 activation is bf16 [3][C / 16][M][16].
 namespace dmc {
-typedef unsigned x3s_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void x3s_split3(float v, unsigned& u0, unsigned& u1, unsigned& u2) {
-    u0 = __float_as_uint(v);
-    const float r1 = v - __uint_as_float(u0 & 0xffff0000u);
-    u1 = __float_as_uint(r1);
-    u2 = __float_as_uint(r1 - __uint_as_float(u1 & 0xffff0000u));
-}
 // the three slices of 8 consecutive channels (8 g .. 8 g + 7) of pixel m -> xs
 __device__ __forceinline__ void x3s_store8(unsigned short* __restrict__ xs, const float (&v)[8], size_t M, int nchunk, size_t m, int g) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x3s_split3(v[e], u0[e], u1[e], u2[e]);
-    x3s_u32x4 s0, s1, s2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        s0[e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
-        s1[e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
-        s2[e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
-    }
+    const Split3 sp = split8(v);
     const size_t plane = M * 16;
     const size_t w = ((size_t)(g >> 1) * M + m) * 16 + (size_t)(g & 1) * 8;
-    *reinterpret_cast<x3s_u32x4*>(xs + w) = s0;
-    *reinterpret_cast<x3s_u32x4*>(xs + (size_t)nchunk * plane + w) = s1;
-    *reinterpret_cast<x3s_u32x4*>(xs + (size_t)2 * nchunk * plane + w) = s2;
+    *reinterpret_cast<u32x4*>(xs + w) = sp.s[0];
+    *reinterpret_cast<u32x4*>(xs + (size_t)nchunk * plane + w) = sp.s[1];
+    *reinterpret_cast<u32x4*>(xs + (size_t)2 * nchunk * plane + w) = sp.s[2];
 }
 // the three slices of 4 consecutive channels (4 q .. 4 q + 3) of pixel m -> xs: the same split and packing as x3s_store8, in
 // 8-byte pieces (the eval epilogues of conv_x3s.hip / conv_x3q.hip, whose lanes hold four channels of a pixel)
-typedef unsigned x3s_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void x3s_store4(unsigned short* __restrict__ xs, const float (&v)[4], size_t M, int nchunk, size_t m, int q) {
-    unsigned u0[4], u1[4], u2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x3s_split3(v[e], u0[e], u1[e], u2[e]);
-    x3s_u32x2 s0, s1, s2;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        s0[e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
-        s1[e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
-        s2[e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
-    }
+    const Split3x2 sp = split4(v);
     const size_t plane = M * 16;
     const size_t w = ((size_t)(q >> 2) * M + m) * 16 + (size_t)(q & 3) * 4;
-    *reinterpret_cast<x3s_u32x2*>(xs + w) = s0;
-    *reinterpret_cast<x3s_u32x2*>(xs + (size_t)nchunk * plane + w) = s1;
-    *reinterpret_cast<x3s_u32x2*>(xs + (size_t)2 * nchunk * plane + w) = s2;
+    *reinterpret_cast<u32x2*>(xs + w) = sp.s[0];
+    *reinterpret_cast<u32x2*>(xs + (size_t)nchunk * plane + w) = sp.s[1];
+    *reinterpret_cast<u32x2*>(xs + (size_t)2 * nchunk * plane + w) = sp.s[2];
 }
 
 // ---- BatchNorm with GIVEN statistics [+ shortcut] [+ ReLU] on one value: the expression and the order of bn_apply_fwd_kernel /

@@ -5,8 +5,6 @@
 
 namespace dmc { namespace fz {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int FZ_RS = 120;                     // floats per LDS row (>= strip width + 2 zero columns)
 constexpr int FZ_MAXSW = 118;                  // widest strip, halo included
 constexpr int FZ_HALO = 6;                     // columns recomputed on the interior side of a strip (one per layer)

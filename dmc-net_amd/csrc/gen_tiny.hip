@@ -298,7 +298,6 @@ __global__ __launch_bounds__(LTHREADS, 4) void gen_layer_kernel(LayerArgs a) {  
 //     the image border, which is exactly the convolution's zero padding).
 // ------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int D_PLANE = LROWS * LTW;               // 2560 floats per channel
 constexpr int D_BUF = LCH * D_PLANE;               // 10240 floats = 40,960 B; x2 = 81,920 B
@@ -314,7 +313,7 @@ __device__ __forceinline__ void layer_dma_chunk(const LayerArgs& a, float* buf, 
         const int yy = ty0 - 1 + row;
         const float* plane = layer_in_plane<MODE, K>(a, n, c0 + c, HW);
         const float* src = (colok && yy >= 0 && yy < a.H) ? plane + (size_t)yy * a.W + 4 * lane : zero;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(buf + rr * LTW), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(buf + rr * LTW), 16, 0, 0);
     }
 }
 
@@ -445,8 +444,6 @@ __global__ __launch_bounds__(LTHREADS, 4) void gen_layer_dma_kernel(LayerArgs a)
 // barriers.  (With every wave issuing its share of the DMA, all of them stalled at issue whenever
 // the CU's miss queue was full, and staging and MFMA time simply added up.)
 // ------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float dpp_shr_fill(float cur, float lane0_value) {   // lane i <- cur[i-1]; lane 0 <- lane0_value
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0_value),
                                                                  __builtin_bit_cast(int, cur), 0x138, 0xf, 0xf, false));
@@ -500,21 +497,12 @@ struct MfmaGeom {
     static constexpr int WL = NCHUNK * CH * 3 * 4 * NTP;           // LDS weight copy, zero rows for channels >= CIN
 };
 
-// LDS-DMA issued through inline assembly: the compiler does not see an LDS write, so it inserts
+// LDS-DMA issued through inline assembly (mma_bf16.h): the compiler does not see an LDS write, so it inserts
 // no s_waitcnt vmcnt(0) in front of the consumers' ds_reads (with the builtin it does, which
 // serialises every prefetch with the compute it was meant to overlap).  Completion is tracked
 // by hand with s_waitcnt vmcnt(<row transfers per chunk>): "everything but the newest chunk has landed".
-__device__ __forceinline__ void dma_row4(unsigned long long src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off"
-                 :: "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
-
-// scalar row base + per-lane byte offset: the producer's address arithmetic is all SALU, it never
-// competes with the consumers' MFMAs for the vector issue port
-__device__ __forceinline__ void dma_row16_s(unsigned long long sbase, unsigned voff, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :: "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
+// The row transfers use the scalar row base + per-lane byte offset form (lds_dma16_sgpr): the producer's address arithmetic is
+// all SALU, it never competes with the consumers' MFMAs for the vector issue port.
 
 struct RingArgs {
     LayerArgs a;
@@ -559,14 +547,14 @@ __device__ __forceinline__ void ring_stage(const LayerArgs& a, unsigned slot_byt
         if (interior) {
 #pragma unroll
             for (int row = 0; row < P_ROWS; ++row) {
-                dma_row16_s(sptr, voff, dst + row * (LTW * 4));
+                lds_dma16_sgpr(sptr, voff, dst + row * (LTW * 4));
                 sptr += sstride;
             }
         } else {
 #pragma unroll
             for (int row = 0; row < P_ROWS; ++row) {
                 const int yy = ty0 - 1 + row;
-                dma_row16_s((yy >= 0 && yy < a.H) ? sptr : zaddr, voff, dst + row * (LTW * 4));
+                lds_dma16_sgpr((yy >= 0 && yy < a.H) ? sptr : zaddr, voff, dst + row * (LTW * 4));
                 sptr += sstride;
             }
         }
@@ -635,7 +623,7 @@ __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(
     const int tid = threadIdx.x, lane = tid & 63;
     const int r = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave: 0..6 = consumers, 7 = producer
     const float* zero = a.pk + PACKED_TOTAL;
-    const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;          // LDS byte address of the ring
+    const unsigned lds0 = lds_addr_of(lds);          // LDS byte address of the ring
 
     // Tile schedule: workgroups are dispatched round-robin over the 8 XCDs (blockIdx % 8), each with
     // its own L2.  In round k the nwg/8 workgroups of one XCD take nwg/8 CONSECUTIVE tiles (vertically
@@ -812,7 +800,6 @@ __global__ __launch_bounds__(LTHREADS, HALF ? 4 : 2) void gen_layer_mfma_kernel(
 // add / subtract values of like magnitude: measured <= 3x the direct kernels' distance from an fp64 evaluation,
 // tests/test_gen_wino_gpu.py), not bit for bit.
 // ------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // One staged channel's window: three 8-byte reads per row at constant offsets from one address.  VOLATILE loads: the compiler
 // neither pairs them into ds_read2_b64 (half the LDS rate) nor into dword pairs that need an address register each, and it
 // still counts them in its s_waitcnt bookkeeping.
@@ -850,7 +837,7 @@ __global__ __launch_bounds__(LTHREADS, 2) void gen_wino_kernel(RingArgs ra) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int r = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave: 0..6 = consumers, 7 = producer
     const float* zero = a.pk + PACKED_TOTAL;
-    const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
+    const unsigned lds0 = lds_addr_of(lds);
 
     const int nwg = gridDim.x;                                    // XCD-aware tile schedule, as above
     const int t_begin = nwg % 8 == 0 ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
@@ -1119,14 +1106,14 @@ __device__ __forceinline__ void fuse_stage(const LayerArgs& a, unsigned slot_byt
         if (interior) {
 #pragma unroll
             for (int row = 0; row < F_ROWS; ++row) {
-                dma_row16_s(sptr, voff, dst + row * (LTW * 4));
+                lds_dma16_sgpr(sptr, voff, dst + row * (LTW * 4));
                 sptr += sstride;
             }
         } else {
 #pragma unroll
             for (int row = 0; row < F_ROWS; ++row) {
                 const int yy = ty0 - 2 + row;
-                dma_row16_s((yy >= 0 && yy < a.H) ? sptr : zaddr, voff, dst + row * (LTW * 4));
+                lds_dma16_sgpr((yy >= 0 && yy < a.H) ? sptr : zaddr, voff, dst + row * (LTW * 4));
                 sptr += sstride;
             }
         }
@@ -1179,7 +1166,7 @@ __global__ __launch_bounds__(LTHREADS, 2) void gen_l45_kernel(RingArgs ra) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int r = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave: 0..6 = consumers, 7 = producer
     const float* zero = a.pk + PACKED_TOTAL;
-    const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
+    const unsigned lds0 = lds_addr_of(lds);
 
     const int nwg = gridDim.x;
     const int t_begin = nwg % 8 == 0 ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
@@ -1459,14 +1446,14 @@ __device__ __forceinline__ void gather_stage(const LayerArgs& a, unsigned slot_b
     if (interior) {
 #pragma unroll
         for (int row = 0; row < G_ROWS; ++row) {
-            dma_row16_s(sptr, voff, dst + row * (LTW * 4));
+            lds_dma16_sgpr(sptr, voff, dst + row * (LTW * 4));
             sptr += sstride;
         }
     } else {
 #pragma unroll
         for (int row = 0; row < G_ROWS; ++row) {
             const int yy = ty0 - 1 + row;
-            dma_row16_s((yy >= 0 && yy < a.H) ? sptr : zaddr, voff, dst + row * (LTW * 4));
+            lds_dma16_sgpr((yy >= 0 && yy < a.H) ? sptr : zaddr, voff, dst + row * (LTW * 4));
             sptr += sstride;
         }
     }
@@ -1483,7 +1470,7 @@ __global__ __launch_bounds__(G_THREADS) void gen_layer_gather_kernel(RingArgs ra
     const int tid = threadIdx.x, lane = tid & 63;
     const int r = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave: 0..13 consumers, 14..15 producers
     const float* zero = a.pk + PACKED_TOTAL;
-    const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
+    const unsigned lds0 = lds_addr_of(lds);
 
     const int nwg = gridDim.x;
     const int t_begin = nwg % 8 == 0 ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
@@ -1667,8 +1654,6 @@ __global__ __launch_bounds__(G_THREADS) void gen_layer_gather_kernel(RingArgs ra
 // registers) live in registers for the whole launch and are reduced across waves (fixed
 // order) and across workgroups (second kernel, fixed order): deterministic.
 // ------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WT_H = 8, WT_W = 32;
 // tile image: [33 planes][10 rows][40 floats]; a row holds image columns tx0-4 .. tx0+35 (the tile,
 // its halo column on each side and 3+3 unused), i.e. ten 16-byte chunks that are each entirely
@@ -1714,8 +1699,7 @@ __device__ __forceinline__ void wgrad_dma_tile_generic(const WgradArgs& a, float
             const int yy = ty0 - 1 + row;
             const float* base = in_plane(a.mv, a.res, a.feat, n, plane, HW);
             const float* src = (colok && yy >= 0 && yy < a.H) ? base + (size_t)yy * a.W + xx : zero;
-            dma_row4((unsigned long long)src,
-                     (unsigned)(size_t)(lptr_t)(buf + plane * WX_PLANE + row * WX_PITCH + WX_COL0));
+            lds_dma4_off((unsigned long long)src, lds_addr_of(buf + plane * WX_PLANE + row * WX_PITCH + WX_COL0));
         }
     }
 }
@@ -1856,10 +1840,6 @@ constexpr int PW_BUF = (PW_X + PW_G + 3) / 4 * 4;        // 19,116 floats = 76,4
 static_assert(2 * PW_BUF * 4 <= 160 * 1024, "LDS");
 static_assert(WPART <= 2 * PW_BUF, "cross-wave reduction reuses the tile buffers");
 
-__device__ __forceinline__ void dma16_s(unsigned long long sbase, unsigned voff, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :: "v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
 // producer: stage one tile.  Lane L of instruction h (L = 64 h + lane) moves 16-byte chunk
 // (row L / 10, chunk L % 10) of an input plane; lane (row, chunk) = (lane / 8, lane % 8) of a gradient plane.
 // do_x: stage the 33 input planes; gradient planes [gp0, gp1) are staged by the caller too (the bf16x3 consumers take the
@@ -1891,14 +1871,14 @@ __device__ __forceinline__ void wgrad_stage(const WgradArgs& a, float* buf, unsi
         const unsigned long long sbase = (unsigned long long)pb + (unsigned long long)xorg;
         const unsigned dst = buf_byte + (unsigned)(plane * PW_XPLANE) * 4;
         if (x_interior) {
-            dma16_s(sbase, voff0, dst);
-            if (lane < PW_XROWS * 10 - 64) dma16_s(sbase, voff1, dst + 1024);
+            lds_dma16(sbase, voff0, dst);
+            if (lane < PW_XROWS * 10 - 64) lds_dma16(sbase, voff1, dst + 1024);
         } else {
             // edge tile: lanes whose chunk lies outside the image do not transfer; they zero their chunk
             float4* l0 = reinterpret_cast<float4*>(buf + plane * PW_XPLANE) + lane;
-            if (ok0) dma16_s(sbase, voff0, dst); else *l0 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok0) lds_dma16(sbase, voff0, dst); else *l0 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (lane < PW_XROWS * 10 - 64) {
-                if (ok1) dma16_s(sbase, voff1, dst + 1024); else l0[64] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok1) lds_dma16(sbase, voff1, dst + 1024); else l0[64] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
     }
@@ -1915,40 +1895,18 @@ __device__ __forceinline__ void wgrad_stage(const WgradArgs& a, float* buf, unsi
                                          : a.gout + ((size_t)n * 2 + (gp - NFEAT)) * HW;
             const unsigned long long sbase = (unsigned long long)pb + (unsigned long long)gorg;
             const unsigned dst = buf_byte + (unsigned)(PW_X + gp * PW_GPLANE) * 4;
-            if (g_interior) dma16_s(sbase, gvoff, dst);
-            else if (gok) dma16_s(sbase, gvoff, dst);
+            if (g_interior) lds_dma16(sbase, gvoff, dst);
+            else if (gok) lds_dma16(sbase, gvoff, dst);
             else reinterpret_cast<float4*>(buf + PW_X + gp * PW_GPLANE)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
 }
 
-// bf16x3 helpers (see conv_nhwc.hip: an fp32 value = the exact sum of three bf16 slices; six slice products per
-// fp32 product on the bf16 matrix cores, fp32 accumulate, error <= one fp32 rounding of the product)
-typedef __bf16 gen_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned gen_u32x4 __attribute__((ext_vector_type(4)));
-struct GenSplit3 { gen_u32x4 s[3]; };
-__device__ __forceinline__ GenSplit3 gen_split_bf16x3(const float (&v)[8]) {
-    unsigned u0[8], u1[8], u2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        u0[e] = __float_as_uint(v[e]);
-        const float r1 = v[e] - __uint_as_float(u0[e] & 0xffff0000u);
-        u1[e] = __float_as_uint(r1);
-        u2[e] = __float_as_uint(r1 - __uint_as_float(u1[e] & 0xffff0000u));
-    }
-    GenSplit3 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        r.s[0][e] = __builtin_amdgcn_perm(u0[2 * e + 1], u0[2 * e], 0x07060302u);
-        r.s[1][e] = __builtin_amdgcn_perm(u1[2 * e + 1], u1[2 * e], 0x07060302u);
-        r.s[2][e] = __builtin_amdgcn_perm(u2[2 * e + 1], u2[2 * e], 0x07060302u);
-    }
-    return r;
-}
-__device__ __forceinline__ f32x4 gen_mfma_x3(const GenSplit3& a, const GenSplit3& b, f32x4 c) {
+// six slice products per fp32 product (bf16x3 arithmetic, mma_bf16.h) on v_mfma_f32_16x16x32_bf16
+__device__ __forceinline__ f32x4 gen_mfma_x3(const Split3& a, const Split3& b, f32x4 c) {
     // small terms first: (0,2) (2,0) (1,1) (0,1) (1,0) (0,0)
     auto mm = [&](int i, int j, f32x4 acc) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gen_bf16x8, a.s[i]), __builtin_bit_cast(gen_bf16x8, b.s[j]), acc, 0, 0, 0);
+        return mfma16(a.s[i], b.s[j], acc);
     };
     c = mm(0, 2, c); c = mm(2, 0, c); c = mm(1, 1, c); c = mm(0, 1, c); c = mm(1, 0, c); c = mm(0, 0, c);
     return c;
@@ -1970,7 +1928,7 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int j = lane & 15, kq = lane >> 4;          // column / pixel-in-group of this lane
     const size_t HW = (size_t)a.H * a.W;
-    const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds2;
+    const unsigned lds0 = lds_addr_of(lds2);
     const int per_frame = a.tiles_x * a.tiles_y;
     const int ntiles = a.N * per_frame;
     const bool producer = wave == PW_H;
@@ -2045,12 +2003,12 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
             av[0] = p0.x; av[1] = p0.y; av[2] = p0.z; av[3] = p0.w; av[4] = p1.x; av[5] = p1.y; av[6] = p1.z; av[7] = p1.w;
 #pragma unroll
             for (int e = 0; e < 8; ++e) bias_a += av[e];
-            const GenSplit3 a0s = gen_split_bf16x3(av);
+            const Split3 a0s = split8(av);
             const float4 q0 = *reinterpret_cast<const float4*>(lds + offA1 + sA), q1 = *reinterpret_cast<const float4*>(lds + offA1 + sA + 4);
             av[0] = q0.x; av[1] = q0.y; av[2] = q0.z; av[3] = q0.w; av[4] = q1.x; av[5] = q1.y; av[6] = q1.z; av[7] = q1.w;
 #pragma unroll
             for (int e = 0; e < 8; ++e) av[e] = rowB ? av[e] : 0.f;
-            const GenSplit3 a1s = gen_split_bf16x3(av);
+            const Split3 a1s = split8(av);
 #pragma unroll
             for (int gt = 0; gt < 7; ++gt) {
                 float wv[10];
@@ -2060,7 +2018,6 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
                 // serviced in 16-byte slots of the 256-byte bank row: modelled 180 LDS cycles per wave and tile
                 // where the dword reads take 640
                 const float* wp = lds + offW[gt] + wave * WX_PITCH;
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
                 const f32x2 e0 = *static_cast<const f32x2*>(__builtin_assume_aligned(wp - 1, 8));
                 const f32x4 m0 = *static_cast<const f32x4*>(__builtin_assume_aligned(wp + 1, 16));
                 const f32x4 m1 = *static_cast<const f32x4*>(__builtin_assume_aligned(wp + 5, 16));
@@ -2073,23 +2030,18 @@ __global__ __launch_bounds__(512, 2) void gen_bwd_weight_pc_kernel(WgradArgs a) 
                 }
                 unsigned u[3][10];
 #pragma unroll
-                for (int e = 0; e < 10; ++e) {
-                    u[0][e] = __float_as_uint(wv[e]);
-                    const float r1 = wv[e] - __uint_as_float(u[0][e] & 0xffff0000u);
-                    u[1][e] = __float_as_uint(r1);
-                    u[2][e] = __float_as_uint(r1 - __uint_as_float(u[1][e] & 0xffff0000u));
-                }
+                for (int e = 0; e < 10; ++e) split3(wv[e], u[0][e], u[1][e], u[2][e]);
                 unsigned P[3][5], Q[3][4];
 #pragma unroll
                 for (int sl = 0; sl < 3; ++sl) {
 #pragma unroll
-                    for (int k = 0; k < 5; ++k) P[sl][k] = __builtin_amdgcn_perm(u[sl][2 * k + 1], u[sl][2 * k], 0x07060302u);
+                    for (int k = 0; k < 5; ++k) P[sl][k] = pack_hi(u[sl][2 * k + 1], u[sl][2 * k]);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) Q[sl][k] = __builtin_amdgcn_perm(u[sl][2 * k + 2], u[sl][2 * k + 1], 0x07060302u);
+                    for (int k = 0; k < 4; ++k) Q[sl][k] = pack_hi(u[sl][2 * k + 2], u[sl][2 * k + 1]);
                 }
 #pragma unroll
                 for (int dxi = 0; dxi < 3; ++dxi) {
-                    GenSplit3 bs;
+                    Split3 bs;
 #pragma unroll
                     for (int sl = 0; sl < 3; ++sl)
 #pragma unroll

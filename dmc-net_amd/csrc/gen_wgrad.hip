@@ -36,10 +36,6 @@ namespace dmc {
 namespace {
 using namespace fz;
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int WR_THREADS = 1024;                                       // 8 consumer + 8 splitter waves
 constexpr int SW = 32;                                                  // strip width = one MFMA k-block per image row
 #ifndef WR_PRIO
@@ -204,10 +200,10 @@ __device__ __forceinline__ unsigned sel_mask(unsigned if0, unsigned if1, mask_t 
     return r;
 }
 
-// the three bf16 slices of four pixels, as 16-bit values in the high halves
+// the three bf16 slices of four pixels, as 16-bit values in the high halves: split3 (mma_bf16.h) on four values, the same
+// arithmetic written on pairs
 struct Split4 { unsigned u[3][4]; };
-__device__ __forceinline__ Split4 split4(f32x4 v) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ Split4 split4_pk(f32x4 v) {
     Split4 r;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                                       // (pairs: the subtractions become v_pk_add_f32)
@@ -286,17 +282,17 @@ __device__ __forceinline__ void run_splitter(const WrArgs& a, unsigned* lds, int
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const Split4 sp = split4(g.r[s]);
+            const Split4 sp = split4_pk(g.r[s]);
             if (tk[s].flags & 2) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     u32x2 w;
-                    w.x = __builtin_amdgcn_perm(sp.u[q][1], sp.u[q][0], 0x07060302u);
-                    w.y = __builtin_amdgcn_perm(sp.u[q][3], sp.u[q][2], 0x07060302u);
+                    w.x = pack_hi(sp.u[q][1], sp.u[q][0]);
+                    w.y = pack_hi(sp.u[q][3], sp.u[q][2]);
                     *reinterpret_cast<u32x2*>(lds + tk[s].lds + RING * 2 * XROW + q * XSL) = w;
                 }
             }
-            last[s].x = __builtin_amdgcn_perm(sp.u[1][3], sp.u[0][3], 0x07060302u);   // the last pixel's slices 0 | 1
+            last[s].x = pack_hi(sp.u[1][3], sp.u[0][3]);   // the last pixel's slices 0 | 1
             last[s].y = sp.u[2][3] >> 16;                                              // slice 2
         }
 #pragma unroll
@@ -336,11 +332,10 @@ __device__ __forceinline__ void run_splitter(const WrArgs& a, unsigned* lds, int
 }
 
 // ---- consumers -----------------------------------------------------------------------------------------------------------------
-struct Frag3 { u32x4 s[3]; };
-__device__ __forceinline__ f32x4 mfma_x3(const Frag3& x, const Frag3& y, f32x4 c) {
+__device__ __forceinline__ f32x4 mfma_x3(const Split3& x, const Split3& y, f32x4 c) {
     // small terms first: (0,2) (2,0) (1,1) (0,1) (1,0) (0,0)
     auto mm = [&](int i, int j, f32x4 acc) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x.s[i]), __builtin_bit_cast(bf16x8, y.s[j]), acc, 0, 0, 0);
+        return mfma16(x.s[i], y.s[j], acc);
     };
     c = mm(0, 2, c); c = mm(2, 0, c); c = mm(1, 1, c); c = mm(0, 1, c); c = mm(1, 0, c); c = mm(0, 0, c);
     return c;
@@ -391,7 +386,7 @@ __device__ __forceinline__ void run_consumer(const WrArgs& a, unsigned* lds, int
     cs.init(a, s0);
     auto work = [&](auto phc) {
         constexpr int PH = decltype(phc)::value;
-        Frag3 a0, am;                          // gradient pixels x (taps dx = 0, 1) and x - 1 (dx = 2)
+        Split3 a0, am;                          // gradient pixels x (taps dx = 0, 1) and x - 1 (dx = 2)
         {
             const u32x2 e = *reinterpret_cast<const u32x2*>(lds + offeg + PH * 2 * EROW);   // halfwords: slice 0 | 1, 2
 #pragma unroll
@@ -406,7 +401,7 @@ __device__ __forceinline__ void run_consumer(const WrArgs& a, unsigned* lds, int
 #endif
 #pragma unroll
         for (int w = 0; w < C::NW; ++w) {
-            Frag3 b0, bm;                      // input pixels x (dx = 1, 2) and x - 1 (dx = 0)
+            Split3 b0, bm;                      // input pixels x (dx = 1, 2) and x - 1 (dx = 0)
             const u32x2 e = *reinterpret_cast<const u32x2*>(lds + offex[PH][w]);
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
@@ -421,9 +416,9 @@ __device__ __forceinline__ void run_consumer(const WrArgs& a, unsigned* lds, int
         if constexpr (C::ONES) {               // bias of tile A: the aligned fragment against ones (slices 1, 2 of one are zero)
             const u32x4 one = (u32x4){ONE_PAIR, ONE_PAIR, ONE_PAIR, ONE_PAIR};
             f32x4 c = acc[9];
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a0.s[2]), __builtin_bit_cast(bf16x8, one), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a0.s[1]), __builtin_bit_cast(bf16x8, one), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a0.s[0]), __builtin_bit_cast(bf16x8, one), c, 0, 0, 0);
+            c = mfma16(a0.s[2], one, c);
+            c = mfma16(a0.s[1], one, c);
+            c = mfma16(a0.s[0], one, c);
             acc[9] = c;
         }
     };
@@ -491,10 +486,8 @@ __device__ __forceinline__ void cold_fill(const WrArgs& a, unsigned* lds, const 
                                                                                    : a.feat + ((size_t)sg.n * NFEAT + (P - 5)) * HW)
                               : (P < NFEAT ? a.gbuf + ((size_t)sg.n * NFEAT + P) * HW : a.gout + ((size_t)sg.n * 2 + (P - NFEAT)) * HW);
         const float v = row >= 0 && row < a.H ? pl[(size_t)row * a.W + col] : 0.f;
-        const unsigned u0 = __float_as_uint(v);
-        const float r1 = v - __uint_as_float(u0 & 0xffff0000u);
-        const unsigned u1 = __float_as_uint(r1);
-        const unsigned u2 = __float_as_uint(r1 - __uint_as_float(u1 & 0xffff0000u));
+        unsigned u0, u1, u2;
+        split3(v, u0, u1, u2);
         const int e = C0 + (isx ? 0 : CKIND) + 2 * (P * CPITCH + ridx);
         lds[e] = (u0 >> 16) | (u1 & 0xffff0000u);
         lds[e + 1] = u2 >> 16;

@@ -23,7 +23,7 @@ inline size_t gen_x3_frag_bytes() { return (size_t)gx_frag_off(GX_LAYERS) * 1024
 // One thread of the fragment pack (called by gen_tiny.hip's parameter-pack kernel for its threads beyond the fp32 block: no
 // launch of its own).  A fragments: [layer][row tile][k-block][slice][lane][8 bf16]; lane (i, kq): row R = 16 rt + i = (dy, co) =
 // (R / 8, R % 8), k = 8 kq + j of k-block kb = group g = 4 kb + kq = (dx, chunk) = (g / NCH, g % NCH), channel 8 chunk + j (physical
-// channel order: dmc_common.h); truncation split into three bf16 slices as everywhere (conv_nhwc.hip)
+// channel order: dmc_common.h); truncation split into three bf16 slices as everywhere (mma_bf16.h)
 __device__ __forceinline__ void gen_x3_pack_thread(const ParamPtrs& P, unsigned short* __restrict__ frags, int t) {
     int K = 0, base = 0;
     while (K < GX_LAYERS && t >= (base + gx_nfrag(K) / 3) * 512) { base += gx_nfrag(K) / 3; ++K; }
@@ -35,14 +35,12 @@ __device__ __forceinline__ void gen_x3_pack_thread(const ParamPtrs& P, unsigned 
     const int dy = R >> 3, co = R & 7, dx = g / nch, ci = 8 * (g % nch) + j;
     float w = 0.f;
     if (R < 24 && co < cout && g < G && ci < cin) w = P.w[K][(co * cin + logical_of(K, ci)) * 9 + dy * 3 + dx];
-    const unsigned u0 = __float_as_uint(w);
-    const float r1 = w - __uint_as_float(u0 & 0xffff0000u);
-    const unsigned u1 = __float_as_uint(r1);
-    const unsigned u2 = __float_as_uint(r1 - __uint_as_float(u1 & 0xffff0000u));
+    unsigned s0, s1, s2;
+    split3_bf16(w, s0, s1, s2);
     unsigned short* dst = frags + ((size_t)(gx_frag_off(K) + f * 3) * 64 + lane) * 8 + j;
-    dst[0] = (unsigned short)(u0 >> 16);
-    dst[512] = (unsigned short)(u1 >> 16);
-    dst[1024] = (unsigned short)(u2 >> 16);
+    dst[0] = (unsigned short)s0;
+    dst[512] = (unsigned short)s1;
+    dst[1024] = (unsigned short)s2;
 }
 #endif
 

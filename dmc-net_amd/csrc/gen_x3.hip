@@ -3,7 +3,7 @@
 // Reference behaviour: code/dmcnet/model.py:172-194 (EstimatorDenseNetTiny: conv 3x3 + LeakyReLU(0.1), dense concatenation),
 // :111-119 (conv).  The fp32 kernels of gen_tiny.hip run these layers on v_mfma_f32_4x4x1 -- the only fp32 MFMA shape that fits
 // 6 / 8 output channels -- and are bound by their consumer loop (LDS operand reads + 9-cycle MFMAs + the push epilogue), not by
-// memory.  Here an fp32 value is the exact sum of three bf16 slices (conv_nhwc.hip), six slice products per
+// memory.  Here an fp32 value is the exact sum of three bf16 slices (mma_bf16.h), six slice products per
 // product block, fp32 accumulate: fp32-level error at 2.67x fewer matrix cycles, and the 16 x 16 x 32 shape is filled by
 // putting the VERTICAL taps into the rows:
 //
@@ -28,11 +28,9 @@
 // (pixel stride = an odd number of 16-byte words: conflict-free) -- no workgroup barrier anywhere.  Output: + bias,
 // LeakyReLU(0.1), planar stores (64-byte runs per plane and instruction).
 #include "dmc_common.h"
-#include "x3s_common.h"
 #include "gen_x3.h"
 
 using namespace dmc;
-using namespace dmc::x3;
 
 namespace {
 
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(GX_WAVES * 64, 2) void gen_x3_kernel(GenX3Args a) {
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             u32x4 s0, s1, s2;
-            split8(make_float4(v[c][0], v[c][1], v[c][2], v[c][3]), make_float4(v[c][4], v[c][5], v[c][6], v[c][7]), s0, s1, s2);
+            split8(v[c], s0, s1, s2);
             if (pl < 30) {
                 *reinterpret_cast<u32x4*>(wr + 16 * c) = s0;
                 *reinterpret_cast<u32x4*>(wr + 16 * c + PL) = s1;

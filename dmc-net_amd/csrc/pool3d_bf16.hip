@@ -21,8 +21,6 @@ using namespace dmc;
 namespace {
 
 typedef unsigned short bf16_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct Pool3dArgs {
     const bf16_t* x;       // [N][D][H][W][C]   (backward: unused)

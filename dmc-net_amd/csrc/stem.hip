@@ -97,11 +97,11 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_kernel(StemArgs a) {
     const int per_frame = a.tiles_x * a.tiles_y;
     const int ntiles = a.N * per_frame;
 
-    mfma_f32x4 acc[S_MT][S_NT];
+    f32x4 acc[S_MT][S_NT];
 #pragma unroll
     for (int m = 0; m < S_MT; ++m)
 #pragma unroll
-        for (int t = 0; t < S_NT; ++t) acc[m][t] = (mfma_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < S_NT; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     if (wave == S_TH) {
         // ------------------------------ producer wave ------------------------------
@@ -201,7 +201,6 @@ __global__ void stem_reduce2_kernel(const float* __restrict__ partials, int grou
 // 16-byte stores).  Replaces MIOpen's implicit-GEMM forward (0.25 ms at 120 frames), the last library convolution of
 // config 2.
 // ------------------------------------------------------------------------------------------
-typedef float stem_f32x16 __attribute__((ext_vector_type(16)));
 
 struct StemFwdArgs {
     const float* x;        // [N, 2, H, W]
@@ -270,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(StemFwdArgs a) {
     for (; tile < ntiles; tile += stride) {
         const long next = tile + stride;
         if (next < ntiles) load_tile(next, xn);
-        stem_f32x16 acc[2];
+        f32x16 acc[2];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(StemFwdArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// The same forward in bf16x3 arithmetic (conv_nhwc.hip: fp32 = the exact sum of three bf16 slices; six slice products
+// The same forward in bf16x3 arithmetic (mma_bf16.h: fp32 = the exact sum of three bf16 slices; six slice products
 // per fp32 product on v_mfma_f32_32x32x16_bf16, fp32 accumulate, error <= one fp32 rounding of the product), on the
 // scheme of the I3D stem (stem3d_bf16.hip): the input is first written as three zero-padded bf16 slice volumes
 // [3][N][H+6][Wp] of (channel 0, channel 1) dwords, in which the 7 taps x 2 channels (+ 2 zero-weight slots) of a kernel
@@ -305,18 +304,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_kernel(StemFwdArgs a) {
 // = 84 MFMAs of 32 cycles per 32-pixel tile where the fp32 form issues 98 of 64; the split weights [3][7][64][16] (43 KB)
 // sit in LDS; persistent 8-wave workgroups.
 // ------------------------------------------------------------------------------------------
-typedef __bf16 stem_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned stem_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned stem_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int SX_WLDS = 3 * 7 * S_CO * 32;                // 43,008 bytes
-
-__device__ __forceinline__ void stem_split3(float v, unsigned& s0, unsigned& s1, unsigned& s2) {
-    const unsigned u0 = __float_as_uint(v);
-    const float r1 = v - __uint_as_float(u0 & 0xffff0000u);
-    const unsigned u1 = __float_as_uint(r1);
-    const unsigned u2 = __float_as_uint(r1 - __uint_as_float(u1 & 0xffff0000u));
-    s0 = u0 >> 16; s1 = u1 >> 16; s2 = u2 >> 16;
-}
 
 // x fp32 [N][2][H][W] -> xs [3][N][Hp][Wp] dwords (slice of channel 0 | slice of channel 1 << 16), zero borders (3 in front)
 __global__ __launch_bounds__(256) void stem_prep_x3_kernel(const float* __restrict__ x, unsigned* __restrict__ xs, int N, int H, int W,
@@ -331,8 +319,8 @@ __global__ __launch_bounds__(256) void stem_prep_x3_kernel(const float* __restri
         unsigned a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0;
         if (h >= 0 && h < H && w >= 0 && w < W) {
             const long o = (long)n * 2 * plane + (long)h * W + w;
-            stem_split3(x[o], a0, a1, a2);
-            stem_split3(x[o + plane], b0, b1, b2);
+            split3_bf16(x[o], a0, a1, a2);
+            split3_bf16(x[o + plane], b0, b1, b2);
         }
         xs[i] = a0 | (b0 << 16); xs[vol + i] = a1 | (b1 << 16); xs[2 * vol + i] = a2 | (b2 << 16);
     }
@@ -345,7 +333,7 @@ __global__ __launch_bounds__(256) void stem_pack_w3_kernel(const float* __restri
     if (i >= 7 * S_CO * 16) return;
     const int j = i & 15, co = (i >> 4) & 63, ky = i >> 10;
     unsigned s0 = 0, s1 = 0, s2 = 0;
-    if (j < 14) stem_split3(w[co * s_co + (j & 1) * s_ci + ky * s_ky + (j >> 1) * s_kx], s0, s1, s2);
+    if (j < 14) split3_bf16(w[co * s_co + (j & 1) * s_ci + ky * s_ky + (j >> 1) * s_kx], s0, s1, s2);
     wp[i] = (unsigned short)s0; wp[7 * S_CO * 16 + i] = (unsigned short)s1; wp[2 * 7 * S_CO * 16 + i] = (unsigned short)s2;
 }
 
@@ -373,7 +361,7 @@ __global__ __launch_bounds__(SX_THREADS) void stem_fwd_x3_kernel(StemX3Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
-    for (int i = tid; i < SX_WLDS / 16; i += SX_THREADS) reinterpret_cast<stem_u32x4*>(wlds3)[i] = reinterpret_cast<const stem_u32x4*>(a.wp)[i];
+    for (int i = tid; i < SX_WLDS / 16; i += SX_THREADS) reinterpret_cast<u32x4*>(wlds3)[i] = reinterpret_cast<const u32x4*>(a.wp)[i];
     __syncthreads();
     const long ntiles = (long)a.N * a.OH * a.tiles_x;
     const long stride = (long)gridDim.x * SX_WAVES;
@@ -398,31 +386,30 @@ __global__ __launch_bounds__(SX_THREADS) void stem_fwd_x3_kernel(StemX3Args a) {
         const int ox = 32 * xt + l31;
         const int oxc = ox < a.OW ? ox : a.OW - 1;
         const unsigned* base = a.xs + ((long)n * a.Hp + 2 * oy) * a.Wp + 2 * oxc + 4 * half;
-        stem_f32x16 acc[2];
+        f32x16 acc[2];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[ct][e] = 0.f;
-        stem_u32x4 xb[7][3];
+        u32x4 xb[7][3];
 #pragma unroll
         for (int ky = 0; ky < 7; ++ky)
 #pragma unroll
             for (int sl = 0; sl < 3; ++sl) {
                 const unsigned* p = base + sl * a.vol + (long)ky * a.Wp;
-                const stem_u32x2 lo = *reinterpret_cast<const stem_u32x2*>(p), hi = *reinterpret_cast<const stem_u32x2*>(p + 2);
-                xb[ky][sl] = stem_u32x4{lo[0], lo[1], hi[0], hi[1]};
+                const u32x2 lo = *reinterpret_cast<const u32x2*>(p), hi = *reinterpret_cast<const u32x2*>(p + 2);
+                xb[ky][sl] = u32x4{lo[0], lo[1], hi[0], hi[1]};
             }
 #pragma unroll
         for (int ky = 0; ky < 7; ++ky)
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
-                stem_u32x4 wf[3];
+                u32x4 wf[3];
 #pragma unroll
                 for (int sl = 0; sl < 3; ++sl)
-                    wf[sl] = *reinterpret_cast<const stem_u32x4*>(wlds3 + ((sl * 7 + ky) * S_CO + 32 * ct) * 32 + woff);
+                    wf[sl] = *reinterpret_cast<const u32x4*>(wlds3 + ((sl * 7 + ky) * S_CO + 32 * ct) * 32 + woff);
                 auto mm = [&](int i, int j) {
-                    acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(stem_bf16x8, wf[i]), __builtin_bit_cast(stem_bf16x8, xb[ky][j]),
-                                                                      acc[ct], 0, 0, 0);
+                    acc[ct] = mfma_bf16(wf[i], xb[ky][j], acc[ct]);
                 };
                 mm(0, 2); mm(2, 0); mm(1, 1); mm(0, 1); mm(1, 0); mm(0, 0);      // small terms first
             }
@@ -501,7 +488,6 @@ __global__ __launch_bounds__(SX_THREADS) void stem_fwd_x3_kernel(StemX3Args a) {
 // matrix of the GEMM + col2im formulation (590 MB at 120 frames) never exists, deterministic.  (Scheme of
 // stem3d_dgrad_kernel, stem3d_bf16.hip.)
 // ------------------------------------------------------------------------------------------
-typedef float stem_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int SD_WAVES = 4, SD_MT = 8;                      // up to 128 output pixels per row
 
 // w [64][2][7][7] by element strides -> wq [3 slices][7 ky][16 j = 2 kx + c][64 co] bf16; j = 14, 15 zero
@@ -511,7 +497,7 @@ __global__ __launch_bounds__(256) void stem_pack_wq3_kernel(const float* __restr
     if (i >= 7 * 16 * S_CO) return;
     const int co = i & 63, j = (i >> 6) & 15, ky = i >> 10;
     unsigned s0 = 0, s1 = 0, s2 = 0;
-    if (j < 14) stem_split3(w[co * s_co + (j & 1) * s_ci + ky * s_ky + (j >> 1) * s_kx], s0, s1, s2);
+    if (j < 14) split3_bf16(w[co * s_co + (j & 1) * s_ci + ky * s_ky + (j >> 1) * s_kx], s0, s1, s2);
     wq[i] = (unsigned short)s0; wq[7 * 16 * S_CO + i] = (unsigned short)s1; wq[2 * 7 * 16 * S_CO + i] = (unsigned short)s2;
 }
 
@@ -521,22 +507,6 @@ struct StemDgArgs {
     float* dx;                  // [N][2][H][W]
     int N, H, W, OH, OW;
 };
-
-__device__ __forceinline__ void stem_split8(const float4 lo, const float4 hi, stem_u32x4 (&sl)[3]) {
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    unsigned u[3][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        u[0][e] = __float_as_uint(v[e]);
-        const float r1 = v[e] - __uint_as_float(u[0][e] & 0xffff0000u);
-        u[1][e] = __float_as_uint(r1);
-        u[2][e] = __float_as_uint(r1 - __uint_as_float(u[1][e] & 0xffff0000u));
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sl[k][e] = __builtin_amdgcn_perm(u[k][2 * e + 1], u[k][2 * e], 0x07060302u);
-}
 
 template <int MTC>                                          // 16-pixel row tiles when known at compile time; 0 = runtime
 __global__ __launch_bounds__(SD_WAVES * 64) void stem_dgrad_x3_kernel(StemDgArgs a) {
@@ -551,19 +521,19 @@ __global__ __launch_bounds__(SD_WAVES * 64) void stem_dgrad_x3_kernel(StemDgArgs
     for (long row = (long)blockIdx.x * SD_WAVES + wave; row < nrows; row += (long)gridDim.x * SD_WAVES) {
         const int h = (int)(row % a.H);
         const int n = (int)(row / a.H);
-        stem_f32x4 acc[SD_MT];
+        f32x4 acc[SD_MT];
 #pragma unroll
-        for (int m = 0; m < SD_MT; ++m) acc[m] = stem_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < SD_MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int ky = (h + 1) & 1; ky < S_K; ky += 2) {
             const int oh2 = h + 3 - ky;
             if (oh2 < 0 || (oh2 >> 1) >= a.OH) continue;
             const float* drow = a.dy + ((long)n * a.OH + (oh2 >> 1)) * a.OW * S_CO;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                stem_u32x4 bf[3];
+                u32x4 bf[3];
 #pragma unroll
                 for (int sl = 0; sl < 3; ++sl)
-                    bf[sl] = *reinterpret_cast<const stem_u32x4*>(a.wq + ((sl * 7 + ky) * 16 + l15) * S_CO + 32 * kb + 8 * kg);
+                    bf[sl] = *reinterpret_cast<const u32x4*>(a.wq + ((sl * 7 + ky) * 16 + l15) * S_CO + 32 * kb + 8 * kg);
                 float4 lo[SD_MT], hi[SD_MT];
 #pragma unroll
                 for (int m = 0; m < SD_MT; ++m) {
@@ -576,11 +546,10 @@ __global__ __launch_bounds__(SD_WAVES * 64) void stem_dgrad_x3_kernel(StemDgArgs
 #pragma unroll
                 for (int m = 0; m < SD_MT; ++m) {
                     if (MTC ? m >= MTC : m >= mtiles) continue;
-                    stem_u32x4 af[3];
-                    stem_split8(lo[m], hi[m], af);
+                    u32x4 af[3];
+                    split8(lo[m], hi[m], af[0], af[1], af[2]);
                     auto mm = [&](int i, int j) {
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(stem_bf16x8, af[i]), __builtin_bit_cast(stem_bf16x8, bf[j]),
-                                                                         acc[m], 0, 0, 0);
+                        acc[m] = mfma16(af[i], bf[j], acc[m]);
                     };
                     mm(0, 2); mm(2, 0); mm(1, 1); mm(0, 1); mm(1, 0); mm(0, 0);      // small terms first
                 }

@@ -21,10 +21,6 @@ using namespace dmc;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short bf16_t;
 
 __device__ __forceinline__ unsigned f2bf(float v) {
@@ -168,8 +164,7 @@ __global__ __launch_bounds__(S3_WAVES * 64) void stem3d_fwd_kernel(Stem3dArgs a)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
                     const u32x4 wf = *reinterpret_cast<const u32x4*>(wk + ct * 1024);
-                    acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, cur[ky]),
-                                                                      acc[ct], 0, 0, 0);
+                    acc[ct] = mfma_bf16(wf, cur[ky], acc[ct]);
                 }
             }
 #pragma unroll
@@ -330,8 +325,7 @@ __global__ __launch_bounds__(256) void stem3d_wgrad_kernel(Stem3dWgArgs a) {
                 const u32x4 af = *reinterpret_cast<const u32x4*>(lds + fa[i] + slot);
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bf[j]),
-                                                                        acc[i][j], 0, 0, 0);
+                    acc[i][j] = mfma_bf16(af, bf[j], acc[i][j]);
             }
         }
     }
@@ -428,11 +422,6 @@ struct Stem3dW2Args {
     long nrows, per_wg;
 };
 
-__device__ __forceinline__ void w2_dma16(const void* src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"((unsigned long long)src), "s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)) : "memory");
-}
-
 template <int U>
 __device__ __forceinline__ void w2_wave(const Stem3dW2Args& a, char* lds) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -478,7 +467,7 @@ __device__ __forceinline__ void w2_wave(const Stem3dW2Args& a, char* lds) {
     auto dma = [&](const bf16_t* base, int kz, int ky, int S) {   // input row (kz, ky) of the output row at `base` into slot S of ring kz
         const int swz = (((S - kz) & 3) << 2) | dcp;
         const bf16_t* src = base + ((long)kz * a.Hp + ky) * 512 + dcp * 128 + ((dpos ^ swz) << 3);
-        w2_dma16(src, lds0 + (unsigned)((kz * W2_SLOTS + (S & (W2_SLOTS - 1))) * 1024));
+        lds_dma16_off(src, lds0 + (unsigned)((kz * W2_SLOTS + (S & (W2_SLOTS - 1))) * 1024));
     };
     u32x4 de[2], dd[2];                                    // dy of pixels 2 pair, 2 pair + 1, two octets
     auto dy_load = [&](int row) {
@@ -582,8 +571,7 @@ __device__ __forceinline__ void w2_wave(const Stem3dW2Args& a, char* lds) {
             for (int mt = 0; mt < 7; ++mt) {
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt)
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[mt]), __builtin_bit_cast(bf16x8, B[nt]),
-                                                                          acc[mt][nt], 0, 0, 0);
+                    acc[mt][nt] = mfma_bf16(af[mt], B[nt], acc[mt][nt]);
                 af[mt] = readA(ksn, mt);
                 if (mt == 0) readB(ksn, C, P);
                 if (mt == 5) {
@@ -698,7 +686,6 @@ __global__ __launch_bounds__(256) void stem3d_w2_reduce_kernel(const float* __re
 // formulation would fill 2 of 16 columns).  The second line is a 1-D fold of the row through LDS.  One wave per input row,
 // fp32 output in the cue's NCDHW layout, deterministic.
 // ------------------------------------------------------------------------------------------
-typedef float s3_f32x4 __attribute__((ext_vector_type(4)));
 
 // w fp32 [64][2][7][7][7] -> wq bf16 [49][16][64]: row (kz * 7 + ky) * 16 + 2 kx + c, 64 channels contiguous; rows 14, 15 zero
 __global__ __launch_bounds__(256) void stem3d_pack_wq_kernel(const float* __restrict__ w, bf16_t* __restrict__ wq) {
@@ -736,9 +723,9 @@ __global__ __launch_bounds__(S3_DG_WAVES * 64) void stem3d_dgrad_kernel(Stem3dDg
         const long nt = row / a.H;
         const int t = (int)(nt % a.T);
         const int n = (int)(nt / a.T);
-        s3_f32x4 acc[S3_DG_MT];
+        f32x4 acc[S3_DG_MT];
 #pragma unroll
-        for (int m = 0; m < S3_DG_MT; ++m) acc[m] = s3_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < S3_DG_MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kz = (t & 1); kz < S3_K; kz += 2) {
             const int od = (t + 2 - kz) >> 1;
             if (t + 2 - kz < 0 || od >= a.OD) continue;
@@ -761,7 +748,7 @@ __global__ __launch_bounds__(S3_DG_WAVES * 64) void stem3d_dgrad_kernel(Stem3dDg
 #pragma unroll
                     for (int m = 0; m < S3_DG_MT; ++m) {
                         if (MTC ? m >= MTC : m >= mtiles) continue;
-                        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[m]), __builtin_bit_cast(bf16x8, bf), acc[m], 0, 0, 0);
+                        acc[m] = mfma16(af[m], bf, acc[m]);
                     }
                 }
             }
@@ -817,11 +804,11 @@ __global__ __launch_bounds__(S3_DG_WAVES * 64) void stem3d_dgrad4_kernel(Stem3dD
         const int t = (int)(nt % a.T);
         const int n = (int)(nt / a.T);
         const int nrow = a.H - h0 < 4 ? a.H - h0 : 4;       // rows of this group inside the image
-        s3_f32x4 acc[4][MTC];
+        f32x4 acc[4][MTC];
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int m = 0; m < MTC; ++m) acc[r][m] = s3_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int m = 0; m < MTC; ++m) acc[r][m] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int kz = (t & 1); kz < S3_K; kz += 2) {
             const int od = (t + 2 - kz) >> 1;
             if (t + 2 - kz < 0 || od >= a.OD) continue;
@@ -848,7 +835,7 @@ __global__ __launch_bounds__(S3_DG_WAVES * 64) void stem3d_dgrad4_kernel(Stem3dD
                         const u32x4 bf = *reinterpret_cast<const u32x4*>(wkz + ky * 16 * S3_CO + 32 * kb);
 #pragma unroll
                         for (int m = 0; m < MTC; ++m)
-                            acc[r][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[m]), __builtin_bit_cast(bf16x8, bf), acc[r][m], 0, 0, 0);
+                            acc[r][m] = mfma16(af[m], bf, acc[r][m]);
                     }
                 }
             }
@@ -937,11 +924,11 @@ __global__ __launch_bounds__(256) void stem3d_dgrad_blk_kernel(Stem3dDgArgs a) {
         const int hb = blk % hblocks, q = blk / hblocks;
         const int tb = q % tblocks, n = q / tblocks;
         const int t = 4 * tb + wave;
-        s3_f32x4 acc[8][D3_MT];
+        f32x4 acc[8][D3_MT];
 #pragma unroll
         for (int r = 0; r < 8; ++r)
 #pragma unroll
-            for (int m = 0; m < D3_MT; ++m) acc[r][m] = s3_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int m = 0; m < D3_MT; ++m) acc[r][m] = f32x4{0.f, 0.f, 0.f, 0.f};
 
         auto row_ok = [&](int od_l, int oh_l) -> bool {
             const int od = 2 * tb - 2 + od_l, oh = 4 * hb - 2 + oh_l;
@@ -1014,8 +1001,7 @@ __global__ __launch_bounds__(256) void stem3d_dgrad_blk_kernel(Stem3dDgArgs a) {
                         if (ky < 0 || ky >= S3_K) continue;
 #pragma unroll
                         for (int m = 0; m < D3_MT; ++m) {
-                            acc[r][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af0[m]),
-                                                                                 __builtin_bit_cast(bf16x8, bf[r][0]), acc[r][m], 0, 0, 0);
+                            acc[r][m] = mfma16(af0[m], bf[r][0], acc[r][m]);
                             if ((m & 1) == 0 && nread < D3_MT) {
                                 af1[nread] = *reinterpret_cast<const u32x4*>(rb + nread * 16 * D3_PITCH + dk);
                                 ++nread;
@@ -1032,8 +1018,7 @@ __global__ __launch_bounds__(256) void stem3d_dgrad_blk_kernel(Stem3dDgArgs a) {
                         if (ky < 0 || ky >= S3_K) continue;
 #pragma unroll
                         for (int m = 0; m < D3_MT; ++m)
-                            acc[r][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af1[m]),
-                                                                                 __builtin_bit_cast(bf16x8, bf[r][1]), acc[r][m], 0, 0, 0);
+                            acc[r][m] = mfma16(af1[m], bf[r][1], acc[r][m]);
                     }
                 }
                 D3_LAP(2)
