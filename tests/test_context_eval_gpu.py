@@ -6,7 +6,11 @@ unit sits at 3-4e-7 on these inputs).  BatchNorm parameters and weights are draw
 are standard normal (about half of the pre-activations are negative: asserted).  The shapes are the smallest at which the kernels
 can go wrong -- see UNIT_SHAPES.  Then: batch isolation and run-to-run bit equality; the whole networks against the reference's
 own outputs (golden G2) and against fp64; the dispatch (no stock convolution in the forward-only paths, DMC_CTX_EVAL's module
-flag, training / autograd untouched); every launching entry point in a guarded arena (tests/abi_arena.py)."""
+flag, training / autograd untouched); every launching entry point in a guarded arena (tests/abi_arena.py).
+
+What the 1e-5 bar cannot see in the middle unit's bf16x3 loop -- a lost third-order slice product, a defect in one tap or one
+16-channel k-block, a wrong slice plane of dmc_ctx_pack_weights -- is held by tests/test_ctx_products_gpu.py: the unit with
+identity statistics, exact cases bit for bit through the LeakyReLU and error tap by tap against the CPU emulation."""
 import copy
 import functools
 

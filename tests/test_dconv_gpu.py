@@ -7,7 +7,12 @@ which the kernels can go wrong -- see SHAPES.  Then: batch independence (also pa
 both gradients, which launches a frozen operand saves, grad_output layouts); the whole networks in train() with model.CTX_TRAIN
 on against the stock route on the same device and an fp64 stock copy (outputs, x.grad, every parameter gradient, every
 BatchNorm buffer; the worst pair measured on an MI355X is in DESIGN 4.22); the dispatch; every launching entry point in a
-guarded arena (tests/abi_arena.py)."""
+guarded arena (tests/abi_arena.py).
+
+The 1e-5 bar on dense Gaussian operands cannot see a lost or mis-paired third-order slice product, a defect confined to one tap or
+one 16-channel k-block of the weight panel, a wrong slice plane in the pack or a mirrored tap on the wrong panel of the transposed
+pack: tests/test_ctx_products_gpu.py holds these kernels (and the packs, bit for bit) to the six-product bars of
+tests/test_x3_products_gpu.py on the SHAPES below."""
 import copy
 import functools
 

@@ -409,11 +409,12 @@ def fwd_like_statistics(name, run, act, wt, k, stride, pad, dgrad_to=None, taps=
         hold_to_emulation("%s tap %d" % (name, tap), rows(got), col[:, ks], mat[ks], R.ORDER_WEIGHT_OUTER, conv32)
 
 
-def wgrad_statistics(name, dw, x, dy, k, stride, pad):
+def wgrad_statistics(name, dw, x, dy, k, stride, pad, dilation=1):
     """dw [Cout, Cin, k, k] of one launch on dense operands, grouped by tap x 64-wide output-channel block (taps merged where
-    a block holds fewer than 1000 outputs); K runs over the pixels."""
+    a block holds fewer than 1000 outputs); K runs over the pixels.  A group without a single live output (a dilated tap that
+    lies outside the frame for every pixel) must be all zeros; every other group must hold >= 1000 LIVE outputs."""
     cout, cin = dw.shape[0], dw.shape[1]
-    a, b = R.wgrad_operands(x, dy, k, stride, pad)
+    a, b = R.wgrad_operands(x, dy, k, stride, pad, dilation)
     got = dw.detach().double().cpu().permute(0, 2, 3, 1).reshape(cout, k * k * cin).numpy()
     block = min(64, cout)
     per_tap = block * cin
@@ -427,6 +428,10 @@ def wgrad_statistics(name, dw, x, dy, k, stride, pad):
         for c0, c1 in R.channel_groups(cout, (t1 - t0) * cin):
             sl = (slice(c0, c1), slice(t0 * cin, t1 * cin))
             assert ref[sl].size >= R.MIN_GROUP
+            if not (bound[sl] > 0).any():
+                assert not got[sl].any() and not np.isnan(got[sl]).any(), (name, "taps", t0, t1, "is not all zeros")
+                continue
+            assert int((bound[sl] > 0).sum()) >= R.MIN_GROUP
             worst_rms = max(worst_rms, R.rms_metric(got[sl], ref[sl], bound[sl]) / R.rms_metric(emu[sl], ref[sl], bound[sl]))
             worst_max = max(worst_max, R.max_metric(got[sl], ref[sl], bound[sl]) / emu_max)
     report(name, worst_rms, worst_max, "old metric %.2e" % R.old_metric(got, ref))

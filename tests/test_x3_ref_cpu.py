@@ -13,6 +13,11 @@ kernels to.  Three questions, none of which needs a kernel:
     them.  Two accumulation orders of the CORRECT emulation must agree to within a third of the bar (the order a kernel
     happens to use is not what the bar measures); read as: |metric(order A) - metric(order B)| <= bar / 3 in every group.
 
+The same three questions for the dilated kernels of the ContextNetwork (tests/test_ctx_products_gpu.py): the dilated im2col
+GEMMs against F.conv2d(dilation=d, padding=d) and its gradients, the seeded defects at K = 32 with 32 .. 128 output columns
+(the weakest, one product lost in one 16-channel chunk, is 24 x the rms bar), the value family for kernels that split both
+operands in the loop, and the numpy weight pack.
+
 Measured here (rms metric, Gaussian operands): correct 1.9e-8 .. 2.2e-8; a third-order product lost in the tap 7e-7 .. 2e-6;
 (1,1) lost in one 16-channel chunk 1.0e-6 (Cin 64), 1.4e-7 (Cin 512); the figures are printed by the tests."""
 import numpy as np
@@ -228,3 +233,125 @@ def test_two_accumulation_orders_agree_within_a_third_of_the_bar(cin):
         assert np.all(np.abs(ma - mb) <= (4 * wa) / 3)
         assert np.all(rb <= 3 * ra) and np.all(mb <= 4 * wa)
     assert max(r1.max(), r2.max()) <= 2.0 ** -24
+
+
+# ---------------------------------------------------------------- the dilated kernels of the ContextNetwork (tests/test_ctx_products_gpu.py)
+@pytest.mark.parametrize("d,h,w", [(1, 7, 6), (2, 7, 6), (2, 5, 2), (16, 35, 35), (16, 20, 12), (16, 9, 40)])
+def test_dilated_im2col_gemms_are_the_dilated_convolution_and_its_gradients(d, h, w):
+    """padding = dilation = d, 3 x 3, stride 1; the frames include W <= d (every horizontal side tap outside), H <= d and the
+    35 x 35 frame in which only the 3 x 3 centre pixels see all nine taps at d = 16."""
+    n, cin, cout, k = 2, 3, 4, 3
+    r = rs(17)
+    x, wt = r.standard_normal((n, cin, h, w)), r.standard_normal((cout, cin, k, k))
+    xo, wo = torch.from_numpy(x).requires_grad_(True), torch.from_numpy(wt).requires_grad_(True)
+    yo = F.conv2d(xo, wo, None, 1, d, d)
+    assert tuple(yo.shape) == (n, cout, h, w)
+    g = r.standard_normal(tuple(yo.shape))
+    (yo * torch.from_numpy(g)).sum().backward()
+    col = R.im2col(x, k, 1, d, d)
+    assert np.abs(R.col2nchw(col @ R.weight_matrix(wt), n, h, w) - yo.detach().numpy()).max() < 1e-12
+    dx = R.col2nchw(R.im2col_dgrad(g, k, 1, d, h, w, d) @ R.weight_matrix_dgrad(wt), n, h, w)
+    assert np.abs(dx - xo.grad.numpy()).max() < 1e-12
+    a, b = R.wgrad_operands(x, g, k, 1, d, d)
+    assert np.abs(R.dw_from_matrix(a @ b, cin, k) - wo.grad.numpy()).max() < 1e-12
+    for tap in range(9):                                       # a tap that lies outside for every pixel is a zero column block
+        ky, kx = divmod(tap, 3)
+        outside = (w <= d and kx != 1) or (h <= d and ky != 1)
+        assert (not col[:, tap * cin:(tap + 1) * cin].any()) == outside, tap
+    if d == 16 and h == 35:
+        sees_all = (col.reshape(n, h, w, 9, cin) != 0).all(axis=(3, 4))
+        assert sees_all.sum() == 9 * n and sees_all[:, 16:19, 16:19].all()
+
+
+def test_default_dilation_leaves_the_helpers_bit_identical():
+    r = rs(18)
+    x, g = r.standard_normal((2, 5, 9, 8)).astype(np.float32), r.standard_normal((2, 4, 5, 4)).astype(np.float32)
+    assert np.array_equal(R.im2col(x, 3, 2, 1), R.im2col(x, 3, 2, 1, 1))
+    assert np.array_equal(R.im2col_dgrad(g, 3, 2, 1, 9, 8), R.im2col_dgrad(g, 3, 2, 1, 9, 8, 1))
+    cols = [x[:, :, ky:ky + 7, kx:kx + 6].transpose(0, 2, 3, 1).reshape(-1, 5) for ky in range(3) for kx in range(3)]
+    assert np.array_equal(R.im2col(x, 3, 1, 0), np.concatenate(cols, axis=1))                # written out for d = 1, no padding
+
+
+def ctx_defects(a, b):
+    """The seeded defects at the ContextNetwork geometry (K = 32: two 16-chunks)."""
+    A, B = R.split(a), R.split(b)
+    out = {}
+    for p in R.SIX[1:]:
+        out["%s lost in the block" % (p,)] = R.six_product(A, B, keep=drop(p), order=R.ORDER_WEIGHT_OUTER)
+    for p in ((1, 1), (0, 2)):
+        out["%s lost in one 16-channel chunk" % (p,)] = R.six_product(A, B, defect=(16, 32, drop(p)), order=R.ORDER_WEIGHT_OUTER)
+    out["(1,2) in place of (0,2)"] = R.six_product(A, B, keep=drop((0, 2)) + [(1, 2)], order=R.ORDER_WEIGHT_OUTER)
+    out["s1 rounded, s2 not adjusted"] = R.six_product(R.split_rounded_s1(a), B, order=R.ORDER_WEIGHT_OUTER)
+    return out
+
+
+@pytest.mark.parametrize("cols", [32, 64, 96, 128])
+def test_seeded_defects_exceed_the_statistical_bars_at_the_context_geometry(cols):
+    """tests/test_ctx_products_gpu.py keeps the weights live in one tap and one 32-channel block of the contraction, so K = 32;
+    378 rows are its smallest frame (2 x 9 x 21 pixels), 32 .. 128 columns the output widths, grouped as there (96 columns: a
+    64-wide group and the 32-wide tail).  The kernel's order is ORDER_WEIGHT_OUTER; the correct emulation in another order
+    (smallest first, chunks reversed) stays within a third of the bars."""
+    a, b = one_tap_operands(32, 41 + cols, m=378, n=cols)
+    ref, bound = R.fp64_and_bound(a, b)
+    good = R.emulate(a, b, order=R.ORDER_WEIGHT_OUTER)
+    rms0, _ = group_metrics(good, ref, bound)
+    whole_max = R.max_metric(good, ref, bound)
+    groups = R.channel_groups(cols, ref.shape[0])
+    assert groups == {32: [(0, 32)], 64: [(0, 64)], 96: [(0, 64), (64, 96)], 128: [(0, 64), (64, 128)]}[cols]
+    print("\nK 32, %d columns  correct: rms %s  max %.2e  old metric %.2e" % (cols, rms0, whole_max, R.old_metric(good, ref)))
+    assert rms0.max() <= 2.0 ** -24 and R.old_metric(good, ref) < 1e-5
+    for name, got in ctx_defects(a, b).items():
+        rms, mx = group_metrics(got, ref, bound)
+        over_rms, over_max = float((rms / (3 * rms0)).max()), float((mx / (4 * whole_max)).max())
+        print("  %-38s rms x%.1f of the bar  max x%.1f of the bar  old metric %.2e%s" %
+              (name, over_rms, over_max, R.old_metric(got, ref), "  <- passes the old 1e-5 bar" if R.old_metric(got, ref) < 1e-5 else ""))
+        assert max(over_rms, over_max) > 1.0, (name, over_rms, over_max)
+    other = R.emulate(a, b, order=R.ORDER_SMALL_FIRST, reverse=True)
+    assert not np.array_equal(other, good)
+    rms1, max1 = group_metrics(other, ref, bound)
+    _, max0 = group_metrics(good, ref, bound)
+    assert np.all(np.abs(rms1 - rms0) <= (3 * rms0) / 3) and np.all(np.abs(max1 - max0) <= (4 * whole_max) / 3)
+    assert np.all(rms1 <= 3 * rms0) and np.all(max1 <= 4 * whole_max)
+
+
+def test_loop_family_tells_the_six_products_from_any_other_set():
+    """One term a b of the in-loop family (x3_ref.loop_family): the six-product sum is unit_a unit_b LOOP_CC bit for bit in both
+    issue orders; dropping any one of the six changes the bits; an extra (1,2) or (2,1) changes them at EVERY position of both
+    orders; an extra (2,2) changes them at none (below fp32 resolution)."""
+    r = rs(19)
+    n = 64
+    a, ua = R.loop_family(r, (n, 1))
+    b, ub = R.loop_family(r, (1, n))
+    assert len(np.unique(ua)) > 8 and (ua < 0).any() and (ua > 0).any()
+    want = ua @ ub * R.LOOP_CC                                  # [n, n]: every pair of scales and signs
+    assert np.array_equal(want.astype(np.float32).astype(np.float64), want)
+    assert not np.array_equal(want, (a.astype(np.float64) @ b.astype(np.float64)).astype(np.float32).astype(np.float64))
+    A = [np.concatenate([s, np.zeros((n, 15), np.float32)], axis=1) for s in R.split(a)]     # K = 16 with one live k
+    B = [np.concatenate([s, np.zeros((15, n), np.float32)], axis=0) for s in R.split(b)]
+    for order in (R.ORDER_SMALL_FIRST, R.ORDER_WEIGHT_OUTER):
+        assert np.array_equal(R.six_product(A, B, order=order), want)
+        for lost in R.SIX:
+            assert not (R.six_product(A, B, keep=drop(lost), order=order) == want).any(), (order, lost)
+        for extra in ((1, 2), (2, 1), (2, 2)):
+            for pos in range(7):
+                seq = list(order[:pos]) + [extra] + list(order[pos:])
+                got = R.six_product(A, B, keep=seq, order=seq)
+                if extra == (2, 2):
+                    assert np.array_equal(got, want), (order, pos)
+                else:
+                    assert not (got == want).any(), (order, extra, pos)
+
+
+def test_ctx_pack_layout():
+    """x3_ref.ctx_pack against the element formulas of csrc/ctx_common.h, written out as loops."""
+    r = rs(20)
+    cin, cout = 32, 48
+    w = r.standard_normal((cout, cin, 3, 3)).astype(np.float32)
+    s = R.split(w)
+    fwd, tr = R.ctx_pack(s), R.ctx_pack(s, transposed=True)
+    assert fwd.shape == (9, cin // 16, 3, cout, 16) and tr.shape == (9, cout // 16, 3, cin, 16) and fwd.dtype == np.uint16
+    bits = [R.bf16_bits(p) for p in s]
+    for _ in range(2000):
+        co, ci, t, sl = r.randint(cout), r.randint(cin), r.randint(9), r.randint(3)
+        assert fwd[t, ci // 16, sl, co, ci % 16] == bits[sl][co, ci, t // 3, t % 3]
+        assert tr[t, co // 16, sl, ci, co % 16] == bits[sl][co, ci, (8 - t) // 3, (8 - t) % 3]

@@ -11,6 +11,9 @@ The convolutions and their two gradients are expressed as that GEMM by the im2co
 (forward, data gradient), so "one tap" is a k-range.  Nothing here reads a kernel's result except the two metrics, which
 are functions of fp64 quantities and of ``got`` only.
 
+The im2col helpers take a ``dilation`` (the dilated 3 x 3 convolutions of the ContextNetwork, tests/test_ctx_products_gpu.py);
+``loop_family`` is the value family for kernels that split both operands in the loop, ``ctx_pack`` those kernels' weight panels.
+
 Pairs (i, j) name (slice of the first GEMM operand, slice of the second); the set SIX is symmetric, so which operand is the
 activation does not matter for what is kept, only for the order of issue."""
 import numpy as np
@@ -122,18 +125,20 @@ def out_size(h, k, stride, pad):
     return (h + 2 * pad - k) // stride + 1
 
 
-def im2col(x, k, stride, pad):
-    """x [N, C, H, W] -> [N OH OW, k k C]: column tap * C + c of row (n, oy, ox) is x[n, c, oy stride - pad + ky, ox stride - pad + kx]
-    (zero outside the image), tap = ky k + kx."""
+def im2col(x, k, stride, pad, dilation=1):
+    """x [N, C, H, W] -> [N OH OW, k k C]: column tap * C + c of row (n, oy, ox) is x[n, c, oy stride - pad + ky d, ox stride - pad + kx d]
+    (zero outside the image), tap = ky k + kx, d = ``dilation`` (the dilated 3 x 3 taps of the ContextNetwork read
+    (y + (ky - 1) d, x + (kx - 1) d) with pad = d)."""
     x = np.asarray(x)
     n, c, h, w = x.shape
-    oh, ow = out_size(h, k, stride, pad), out_size(w, k, stride, pad)
+    d = dilation
+    oh, ow = out_size(h, d * (k - 1) + 1, stride, pad), out_size(w, d * (k - 1) + 1, stride, pad)
     xp = np.zeros((n, c, h + 2 * pad + stride, w + 2 * pad + stride), x.dtype)
     xp[:, :, pad:pad + h, pad:pad + w] = x
     cols = []
     for ky in range(k):
         for kx in range(k):
-            t = xp[:, :, ky:ky + stride * oh:stride, kx:kx + stride * ow:stride]
+            t = xp[:, :, ky * d:ky * d + stride * oh:stride, kx * d:kx * d + stride * ow:stride]
             cols.append(t.transpose(0, 2, 3, 1).reshape(n * oh * ow, c))
     return np.concatenate(cols, axis=1)
 
@@ -150,9 +155,9 @@ def col2nchw(y, n, oh, ow):
     return y.reshape(n, oh, ow, -1).transpose(0, 3, 1, 2)
 
 
-def im2col_dgrad(dy, k, stride, pad, h, w):
-    """dy [N, Cout, OH, OW] -> [N H W, k k Cout]: column tap * Cout + co of row (n, y, x) is dy[n, co, (y + pad - ky) / stride,
-    (x + pad - kx) / stride] where both divide and land inside dy, zero elsewhere."""
+def im2col_dgrad(dy, k, stride, pad, h, w, dilation=1):
+    """dy [N, Cout, OH, OW] -> [N H W, k k Cout]: column tap * Cout + co of row (n, y, x) is dy[n, co, (y + pad - ky d) / stride,
+    (x + pad - kx d) / stride] where both divide and land inside dy, zero elsewhere (d = ``dilation``)."""
     dy = np.asarray(dy)
     n, cout, oh, ow = dy.shape
     g = dy.transpose(0, 2, 3, 1)
@@ -161,7 +166,7 @@ def im2col_dgrad(dy, k, stride, pad, h, w):
         for kx in range(k):
             z = np.zeros((n, h, w, cout), dy.dtype)
             oy, ox = np.arange(oh), np.arange(ow)
-            ys, xs = oy * stride - pad + ky, ox * stride - pad + kx
+            ys, xs = oy * stride - pad + ky * dilation, ox * stride - pad + kx * dilation
             vy, vx = (ys >= 0) & (ys < h), (xs >= 0) & (xs < w)
             z[:, ys[vy][:, None], xs[vx][None, :], :] = g[:, oy[vy][:, None], ox[vx][None, :], :]
             cols.append(z.reshape(n * h * w, cout))
@@ -175,12 +180,12 @@ def weight_matrix_dgrad(w):
     return w.transpose(2, 3, 0, 1).reshape(k * k * cout, cin)
 
 
-def wgrad_operands(x, dy, k, stride, pad):
+def wgrad_operands(x, dy, k, stride, pad, dilation=1):
     """Weight gradient as a GEMM over the pixels: (dy as [Cout, P], im2col(x) as [P, k k Cin]); the product is dw as
     [Cout, tap * Cin + ci], so here one tap is a range of OUTPUT columns and K runs over (n, oy, ox)."""
     dy = np.asarray(dy)
     cout = dy.shape[1]
-    return np.ascontiguousarray(dy.transpose(1, 0, 2, 3).reshape(cout, -1)), im2col(x, k, stride, pad)
+    return np.ascontiguousarray(dy.transpose(1, 0, 2, 3).reshape(cout, -1)), im2col(x, k, stride, pad, dilation)
 
 
 def dw_from_matrix(m, cin, k):
@@ -290,6 +295,28 @@ def weight_seen_by_slice(parts, i):
     return sum(parts[j] for j in range(3) if (i, j) in SIX)
 
 
+#: the in-loop family's significand c = 1 + 3 2^-9 + 3 2^-17 and the six-product sum of c c
+LOOP_C = 1.0 + 3.0 * 2.0 ** -9 + 3.0 * 2.0 ** -17
+LOOP_CC = 1.0 + 3.0 * 2.0 ** -8 + 3.0 * 2.0 ** -16 + 9.0 * 2.0 ** -18
+
+
+def loop_family(rs, shape, lo=-3, hi=3):
+    """Values for kernels that split BOTH operands in the loop (no slice tensor can be handed to them): v = +-2^e c with
+    c = 1 + 3 2^-9 + 3 2^-17, e in [lo, hi].  The split is +-2^e (1, 3 2^-9, 3 2^-17) (asserted).  For ONE term a b of two
+    such values the six slice products are 1, 3 2^-9 twice, 3 2^-17 twice and 9 2^-18, times +-2^(e+f): every partial sum is a
+    multiple of 2^-18 below 2, so the sum +-2^(e+f) LOOP_CC is exact in fp32 in any order of issue, and it is NOT the fp32
+    rounding of a b.  Dropping any of the six changes the bits; so does adding (1,2) or (2,1) (9 2^-26 = 1.125 ulp).  Adding
+    (2,2) does NOT: 9 2^-34 lies below fp32 resolution at this magnitude (ulp 2^-23), so this family cannot see a spurious
+    (2,2) product -- nothing with a single term can.  Returns (v, unit) with unit = +-2^e as float64: the expected value of
+    a one-term output is unit_a unit_b LOOP_CC."""
+    unit = np.exp2(rs.randint(lo, hi + 1, size=shape).astype(np.float64)) * rs.choice([-1.0, 1.0], size=shape)
+    v = (unit * LOOP_C).astype(np.float32)
+    assert np.array_equal(v.astype(np.float64), unit * LOOP_C)
+    for got, want in zip(split(v), (1.0, 3.0 * 2.0 ** -9, 3.0 * 2.0 ** -17)):
+        assert np.array_equal(got.astype(np.float64), unit * want)
+    return v, unit
+
+
 def only_tap(w, tap, block=None, width=64, axis=1):
     """Copy of w [Cout, Cin, k, k] that is zero outside tap ``tap`` (= ky k + kx) and, if ``block`` is given, outside the
     ``width``-wide block ``block`` of channel axis ``axis``."""
@@ -330,3 +357,27 @@ def rotate_slices(xs, i):
     out = v.new_zeros(v.shape)
     out[i] = v[0]
     return out.view(-1)
+
+
+def bf16_bits(s):
+    """uint16 bit patterns of an fp32 array that holds bf16 values (asserted)."""
+    s = _np32(s)
+    assert np.array_equal(_trunc16(s), s), "not a bf16 value"
+    return (s.view(np.uint32) >> np.uint32(16)).astype(np.uint16)
+
+
+def ctx_pack(slices, transposed=False):
+    """The weight panels of the dilated gather convolutions (csrc/ctx_common.h), built by the documented layout
+    [9][K / 16][3][R][16] bf16 from three slice arrays [Cout, Cin, 3, 3] (fp32 holding bf16 values).
+      forward:    K = Cin,  R = Cout, element (t, ci, co) = s[co][ci][t];
+      transposed: K = Cout, R = Cin,  element (t', co, ci) = s[co][ci][8 - t'] (the data gradient's mirrored taps).
+    Returns uint16 [9, K / 16, 3, R, 16]."""
+    planes = []
+    for s in slices:
+        b = bf16_bits(s)
+        cout, cin = b.shape[:2]
+        b = b.reshape(cout, cin, 9)
+        m = b[:, :, ::-1].transpose(2, 0, 1) if transposed else b.transpose(2, 1, 0)      # [9, K, R]
+        k, r = m.shape[1:]
+        planes.append(m.reshape(9, k // 16, 16, r).transpose(0, 1, 3, 2))                  # [9, K / 16, R, 16]
+    return np.ascontiguousarray(np.stack(planes, axis=2))
