@@ -120,6 +120,7 @@ struct X3Args {
     int part_blocks = -1;  // host only: rows of stat_part / bnb_part the caller allocated (checked against the grid; -1 = no check)
     int ablate;            // measurement only (option conv_ablate): 16 = no wait for transfers, 32 = no statistics, 64 = no transfers,
                            // 128 = no output stores, 256 = no main loop (results wrong / missing)
+    int bms = 0;           // tile stride in pixels (x3s_tile_stride): the launch's grid on the host, read by the ROWT kernels only
 };
 // EVAL = true (dmc_x3s_conv_bn_eval): the epilogue applies the BatchNorm with GIVEN statistics [+ shortcut] [+ ReLU] to the tile
 // (bn_apply_act1, dmc_common.h) and writes the result as fp32 (y, nullable here) and / or as a slice tensor -- the
@@ -143,9 +144,15 @@ struct X3EvalArgs : X3Args {
 // with ty = 1 (py = 0) or ty in {0, 2} (py = 1), likewise in x: 1 + 2 + 2 + 4 = 9 (tap, class) pairs, every tap feeds
 // exactly one class's accumulators, reading dy at offset (+1 for t = 0, else 0) -- the same step structure, four accumulator
 // sets, no multiply on structural zeros (the in-loop-split path issued four small launches per convolution).
-template <int WM, int WN, int TM, int TN, int PPMAX, bool STAG = false, int CLS = 1, bool EVAL = false>
+// ROWT: ROW-ALIGNED tiles.  Workgroup b starts at pixel b * a.bms, a.bms = (BM / W) W <= BM: a whole number of image rows, so
+// the patch is those rows plus one above and one below (a.bms + 2 W pixels) whatever the tile -- at an arbitrary start BM
+// pixels span one row more, which is what keeps a 512-slot tile of a 56-wide map (9 rows = 504 pixels, patch 616) out of
+// the LDS.  The BM - a.bms slots behind the tile are pixels beyond it, exactly like the slots behind M in a last tile:
+// clamped addresses, nothing stored, zeros into the sums.
+template <int WM, int WN, int TM, int TN, int PPMAX, bool STAG = false, int CLS = 1, bool EVAL = false, bool ROWT = false>
 __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(std::conditional_t<EVAL, X3EvalArgs, X3Args> a) {
     static_assert(!EVAL || CLS == 1, "the eval epilogue belongs to the forward convolution");
+    static_assert(!ROWT || CLS == 1, "row-aligned tiles: forward and stride-1 data gradient");
     constexpr int NW = WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
     static_assert(BN == 64, "packed weight image is 64 rows wide");
     // patch transfers move 32 pixel rows: the staged pixels (<= PPMAX - 1) end on a transfer boundary or the zero row is the
@@ -180,8 +187,9 @@ __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(std::conditional
     // is what lets two workgroups share a CU there.
     const int HW = a.H * a.W, PW = a.W;
     constexpr int ZROW = PPMAX - 1;
-    const int m0 = blockIdx.x * BM;
-    const int mlast = (m0 + BM < a.M ? m0 + BM : a.M) - 1;
+    const int bms = ROWT ? a.bms : BM;                     // tile stride: pixels of a full tile
+    const int m0 = blockIdx.x * bms;
+    const int mlast = (m0 + bms < a.M ? m0 + bms : a.M) - 1;
     const int r_first = m0 / PW, r_last = mlast / PW;      // global pixel rows (n * H + y) of the tile's first / last pixel
     const int f0 = (r_first > 0 ? r_first - 1 : 0) * PW;   // first staged pixel
     const int f1 = (r_last + 2) * PW < a.M ? (r_last + 2) * PW : a.M;   // one past the last staged pixel
@@ -254,6 +262,15 @@ __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(std::conditional
     struct Frag { u32x4 X[TM][3], W[TN][3]; };              // one tap's operands: 3 (TM + TN) reads, 6 TM TN MFMAs
     auto load_frags = [&](auto pbufc, auto wbufc, auto tc, Frag& f) {
         constexpr int pbuf = decltype(pbufc)::value, wbuf = decltype(wbufc)::value, t = decltype(tc)::value;
+        // ROWT: the second patch buffer lies beyond the 64 KB a ds_read's immediate offset reaches, and the compiler keeps a second
+        // copy of all TM x 9 addresses (+ PB) through the main loop, registers this configuration does not have: an opaque copy
+        // makes that one addition per tile and tap happen here
+        int xa[TM];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            xa[i] = xaddr[i][t];
+            if constexpr (ROWT && pbuf == 1) asm volatile("" : "+v"(xa[i]));
+        }
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
 #pragma unroll
@@ -262,7 +279,7 @@ __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(std::conditional
                     L + waddr + (WOFF + wbuf * WB + (((t % 3) * 3 + s) * BN + 32 * j) * 32));
 #pragma unroll
             for (int i = 0; i < TM; ++i)
-                f.X[i][s] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(L + xaddr[i][t] + (pbuf * PB + s * PSL));
+                f.X[i][s] = *reinterpret_cast<const __attribute__((address_space(3))) u32x4*>(L + xa[i] + (pbuf * PB + s * PSL));
         }
     };
     // slice products (weight, input): (0,2) (0,1) (0,0) (1,1) (1,0) (2,0); `between(p)` runs behind product p
@@ -384,6 +401,82 @@ __global__ __launch_bounds__(WM * WN * 64) void x3s_conv_kernel(std::conditional
     char* etile = lds_x3 + wave * ETILE;
     const int mw0 = m0 + wm * TM * 32;                            // first pixel of this wave
     const int rbase = blockIdx.y * BN;
+    if constexpr (ROWT && !EVAL) {
+        if (a.bnb_part) {
+            // Linked BatchNorm-backward sums (below) need an xhat tile beside every d tile, and NW x 64-pixel tiles of both do not
+            // fit the LDS: the wave takes its pixels one 32-pixel tile at a time -- [NW][d, xhat][32][EP], the sums behind them --
+            // and keeps its column sums in registers across the tiles (the pixel order of the sums is the same).  Otherwise the
+            // steps of the training epilogue with the sums linked; such a launch writes no stat_part.
+            constexpr int ET1 = 32 * EP;
+            char* dtile = lds_x3 + wave * 2 * ET1;
+            char* xtile = dtile + ET1;
+            const int c4 = rbase + (lane & 15) * 4;
+            const float4 mean = *reinterpret_cast<const float4*>(a.bnb_stats + c4);
+            const float4 istd = *reinterpret_cast<const float4*>(a.bnb_stats + a.R + c4);
+            double d1 = 0.0, d2 = 0.0;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const bool ok = mw0 + 32 * i + l31 <= mlast;
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        float4 v = make_float4(acc[0][i][j][4 * g], acc[0][i][j][4 * g + 1], acc[0][i][j][4 * g + 2], acc[0][i][j][4 * g + 3]);
+                        if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                        *reinterpret_cast<float4*>(dtile + l31 * EP + (32 * j + 8 * g + 4 * khalf) * 4) = v;
+                    }
+#pragma unroll
+                for (int it = 0; it < 8; ++it) {
+                    const int prow = 4 * it + (lane >> 4);
+                    const int m = mw0 + 32 * i + prow;
+                    float4 v = *reinterpret_cast<const float4*>(dtile + prow * EP + (lane & 15) * 16);
+                    float4 xh = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (m <= mlast) {
+                        const size_t o = (size_t)m * a.R + c4;
+                        if (a.addend) {
+                            const float4 av = *reinterpret_cast<const float4*>(a.addend + o);
+                            v.x += av.x; v.y += av.y; v.z += av.z; v.w += av.w;
+                        }
+                        *reinterpret_cast<float4*>(a.y + o) = v;
+                        const float4 yv = *reinterpret_cast<const float4*>(a.bnb_y + o);
+                        xh = make_float4((yv.x - mean.x) * istd.x, (yv.y - mean.y) * istd.y, (yv.z - mean.z) * istd.z, (yv.w - mean.w) * istd.w);
+                        if (a.bnb_relu) {
+                            unsigned mb;
+                            if (a.bnb_mask) {
+                                mb = a.bnb_mask[o >> 2];
+                            } else {
+                                const float4 g = *reinterpret_cast<const float4*>(a.bnb_gamma + c4), b = *reinterpret_cast<const float4*>(a.bnb_beta + c4);
+                                mb = (fmaf(xh.x, g.x, b.x) > 0.f ? 1u : 0u) | (fmaf(xh.y, g.y, b.y) > 0.f ? 2u : 0u) |
+                                     (fmaf(xh.z, g.z, b.z) > 0.f ? 4u : 0u) | (fmaf(xh.w, g.w, b.w) > 0.f ? 8u : 0u);
+                            }
+                            v.x = (mb & 1) ? v.x : 0.f; v.y = (mb & 2) ? v.y : 0.f; v.z = (mb & 4) ? v.z : 0.f; v.w = (mb & 8) ? v.w : 0.f;
+                        }
+                    }                                             // (pixels beyond the tile: the zeros of `ok`, no contribution)
+                    *reinterpret_cast<float4*>(dtile + prow * EP + (lane & 15) * 16) = v;
+                    *reinterpret_cast<float4*>(xtile + prow * EP + (lane & 15) * 16) = xh;
+                }
+#pragma unroll 8
+                for (int p = 0; p < 32; ++p) {                    // lane = channel, fp64, fixed order
+                    const double d = (double)*reinterpret_cast<const float*>(dtile + p * EP + lane * 4);
+                    const double xh = (double)*reinterpret_cast<const float*>(xtile + p * EP + lane * 4);
+                    d1 += d;
+                    d2 += d * xh;
+                }
+            }
+            double* red = reinterpret_cast<double*>(lds_x3 + NW * 2 * ET1);   // [WM][64][2]
+            red[(wm * 64 + lane) * 2 + 0] = d1;
+            red[(wm * 64 + lane) * 2 + 1] = d2;
+            __syncthreads();
+            for (int cc = tid; cc < BN; cc += NW * 64) {
+                double e1 = 0.0, e2 = 0.0;
+#pragma unroll
+                for (int w = 0; w < WM; ++w) { e1 += red[(w * 64 + cc) * 2 + 0]; e2 += red[(w * 64 + cc) * 2 + 1]; }
+                double* dst = a.bnb_part + ((size_t)blockIdx.x * a.R + rbase + cc) * 2;
+                dst[0] = e1; dst[1] = e2;
+            }
+            return;
+        }
+    }
 #pragma unroll
     for (int cl = 0; cl < CLS; ++cl) {
 #pragma unroll
@@ -547,7 +640,20 @@ struct X3Cfg { int id, BM, PPMAX, threads; };
 // configurations: 0 = 256 pixels, 8 waves (one tile of 32 x 64 each), 1 = 128 pixels, 4 waves, 2 = 64 pixels, 2 waves
 // 4: 128 pixels, 4 waves, a patch of <= 224 pixels (the 28-, 14- and 7-wide maps): 80,064 B of LDS -- TWO workgroups per CU, so that
 // one's prologue / epilogue (20 % of a tile, profiles/r3_x3s_ablation.txt) runs under the other's main loop
-constexpr X3Cfg X3CFGS[] = {{0, 256, 608, 512}, {1, 128, 320, 256}, {2, 64, 192, 128}, {3, 256, 608, 256}, {4, 128, 225, 256}};   // 3 (measurement): 4 waves of 64 x 64
+// 5: 512 pixel SLOTS, 8 waves of 64 x 64 (12 fragment reads per 24 MFMAs instead of 9 per 12; half the weight transfers, prologues,
+// drains and barriers per output), row-aligned tiles (ROWT): stride (512 / W) W pixels, patch = stride + 2 W pixels + the zero row
+// <= 640 -- 56-wide: 9 rows = 504 pixels, patch 617; 28-wide: 504, 561; 14-wide: 504, 533; 7-wide: 511, 526.
+// 2 x 3 x 640 x 32 + 36,864 = 159,744 B of LDS.
+constexpr X3Cfg X3CFGS[] = {{0, 256, 608, 512}, {1, 128, 320, 256}, {2, 64, 192, 128}, {3, 256, 608, 256}, {4, 128, 225, 256},   // 3 (measurement): 4 waves of 64 x 64
+                            {5, 512, 640, 512}};
+
+// tile stride of a configuration: pixels between the starts of consecutive workgroups (= pixels of a full tile); 0: configuration 5
+// has no tile on maps this wide
+int x3s_tile_stride(int cfg, int W) { return cfg == 5 ? (W <= X3CFGS[5].BM ? (X3CFGS[5].BM / W) * W : 0) : X3CFGS[cfg].BM; }
+bool x3s_row_tiles_fit(int W) {
+    const int stride = x3s_tile_stride(5, W);
+    return stride > 0 && stride + 2 * W + 1 <= X3CFGS[5].PPMAX;
+}
 
 bool x3s_shape_ok(int N, int H, int W, int K, int R) {
     if (N <= 0 || H <= 0 || W <= 0 || K % 32 != 0 || R % 64 != 0 || K <= 0 || R <= 0) return false;
@@ -557,8 +663,10 @@ bool x3s_shape_ok(int N, int H, int W, int K, int R) {
 
 int x3s_choose(int N, int H, int W, int R) {
     const long M = (long)N * H * W;
-    const int forced = option(OPT_CONV_CFG);                 // measurement switch: 101 + configuration; 106 = never configuration 4
+    const int forced = option(OPT_CONV_CFG);                 // measurement switch: 101 + configuration; 106 = never configuration 4;
+                                                             // 107 = configuration 5 wherever its patch fits, 108 = never configuration 5
     if (forced >= 101 && forced <= 105 && patch_pixels_max(N, H, W, X3CFGS[forced - 101].BM) <= X3CFGS[forced - 101].PPMAX) return forced - 101;
+    if (forced == 107 && x3s_row_tiles_fit(W)) return 5;
     // the largest tile whose workgroups still cover most of the 256 CUs (measured, 120 frames: 8-wave workgroups of 256
     // pixels win down to layer4's 184 workgroups -- 160-187 TFLOP/s against 123-133 with 64-pixel tiles); else the
     // smallest tile whose patch fits
@@ -567,6 +675,16 @@ int x3s_choose(int N, int H, int W, int R) {
     // workgroups lose 2 % against 184 8-wave ones
     if (forced != 106 && patch_pixels_max(N, H, W, X3CFGS[4].BM) <= X3CFGS[4].PPMAX && ((M + X3CFGS[4].BM - 1) / X3CFGS[4].BM) * (R / 64) >= 512)
         return 4;
+    // row-aligned 512-slot tiles on the 56-wide maps, where the chip's ROUNDS of them are cheaper than those of the 256-pixel tiles: a
+    // workgroup of configuration 5 takes 1.8x the time of one of configuration 0 for twice the pixels (layer1: 46.7 against 25.8 us per
+    // round of 256 CUs), and a launch costs its whole rounds -- 120 frames: 747 workgroups = 3 rounds against 1470 = 6, 0.152 -> 0.140
+    // ms; 96 frames: 3 against 5, +2 %; 83 frames: 3 against 4, +20 % (profiles/x3s_row_tiles_ab.txt; all eight frame counts measured
+    // fall on the side this rule puts them).  28- / 14- / 7-wide maps lose against configurations 4 and 0 (+10 %, +3 %, +58 %).
+    if (forced != 108 && W == 56 && x3s_row_tiles_fit(W) && patch_pixels_max(N, H, W, X3CFGS[0].BM) <= X3CFGS[0].PPMAX) {
+        const long r5 = (((M + x3s_tile_stride(5, W) - 1) / x3s_tile_stride(5, W)) * (R / 64) + 255) / 256;
+        const long r0 = (((M + X3CFGS[0].BM - 1) / X3CFGS[0].BM) * (R / 64) + 255) / 256;
+        if (9 * r5 < 5 * r0) return 5;
+    }
     int fallback = -1;
     for (const X3Cfg& c : X3CFGS) {
         if (c.id > 2 || patch_pixels_max(N, H, W, c.BM) > c.PPMAX) continue;                // (3: by option only)
@@ -581,30 +699,35 @@ int x3s_choose(int N, int H, int W, int R) {
 // transfer pipeline running across tiles (no tile starts by waiting for HBM), transfers issued by half of the waves at a
 // time.  Correct, but 3-6 % SLOWER on every layer (layer1 forward 0.150 vs 0.141 ms): two tile geometries and the
 // cross-tile cases cost 108 spilled SGPRs and 250 wave-uniform branches in the step bodies, more than the hidden prologue.
-template <int WM, int TM, int PPMAX>
+template <int WM, int TM, int PPMAX, bool ROWT = false>
 int launch_x3s(const X3Args& a, hipStream_t s) {
     constexpr int BM = 32 * TM * WM;
-    constexpr size_t op_bytes = 2 * 3 * PPMAX * 32 + 2 * 3 * 3 * 64 * 32, ep_bytes = 2 * (size_t)BM * 272 + 8192;   // d tiles, sums, xhat tiles
+    // epilogue: d tiles, sums, xhat tiles.  ROWT: the waves' tiles and the sums -- with linked sums the d and xhat tiles of one
+    // 32-pixel tile per wave at a time (2 x WM x 32 x 272 + 8192, no more than that)
+    constexpr size_t op_bytes = 2 * 3 * PPMAX * 32 + 2 * 3 * 3 * 64 * 32, ep_bytes = (ROWT ? 1 : 2) * (size_t)BM * 272 + 8192;
     constexpr size_t lds_bytes = op_bytes > ep_bytes ? op_bytes : ep_bytes;
-    dim3 grid((a.M + BM - 1) / BM, a.R / 64);
+    static_assert(lds_bytes <= 160 * 1024 && (!ROWT || 2 * WM * 32 * 272 + 8192 <= lds_bytes), "the tiles exceed the LDS");
+    dim3 grid((a.M + a.bms - 1) / a.bms, a.R / 64);
     // the partials are [gridDim.x][R][2]: sized by the caller with dmc_x3s_conv_stat_blocks(), while the tile configuration is
     // chosen again here (option conv_cfg): refuse a buffer of another height instead of writing past it
     if ((a.stat_part || a.bnb_part) && a.part_blocks >= 0 && (unsigned)a.part_blocks != grid.x)
         return fail(DMC_E_INVALID, "x3s_conv: statistics partials have %d rows but this launch writes %u (dmc_x3s_conv_stat_blocks was "
                                    "called under another conv_cfg option?)", a.part_blocks, grid.x);
     if constexpr (WM >= 4) {
-        if (!(option(OPT_CONV_ABLATE) & 512)) {               // 512: measurement, every wave issues its share behind the barrier
+        if (ROWT || !(option(OPT_CONV_ABLATE) & 512)) {       // 512: measurement, every wave issues its share behind the barrier
             static LdsLimit lim_attr2;
-    const hipError_t attr2 = lim_attr2.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX, true>), (int)lds_bytes);
+    const hipError_t attr2 = lim_attr2.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX, true, 1, false, ROWT>), (int)lds_bytes);
             if (attr2 != hipSuccess) return fail(DMC_E_LAUNCH, "x3s_conv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr2));
-            x3s_conv_kernel<WM, 1, TM, 2, PPMAX, true><<<grid, WM * 64, lds_bytes, s>>>(a);
+            x3s_conv_kernel<WM, 1, TM, 2, PPMAX, true, 1, false, ROWT><<<grid, WM * 64, lds_bytes, s>>>(a);
             return check_launch("x3s_conv");
         }
     }
-    static LdsLimit lim_attr;
-    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX>), (int)lds_bytes);
-    if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "x3s_conv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
-    x3s_conv_kernel<WM, 1, TM, 2, PPMAX><<<grid, WM * 64, lds_bytes, s>>>(a);
+    if constexpr (!ROWT) {                                    // (the row-aligned tiles have the staggered kernel only)
+        static LdsLimit lim_attr;
+        const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX>), (int)lds_bytes);
+        if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "x3s_conv: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
+        x3s_conv_kernel<WM, 1, TM, 2, PPMAX><<<grid, WM * 64, lds_bytes, s>>>(a);
+    }
     return check_launch("x3s_conv");
 }
 
@@ -620,6 +743,7 @@ int run_x3s(const void* xs, const void* wp, const float* addend, float* y, doubl
     a.N = N; a.H = H; a.W = W; a.K = K; a.R = R; a.M = N * H * W;
     a.plane_bytes = (unsigned)a.M * 32u;
     a.part_blocks = part_blocks;
+    a.bms = cfg >= 0 ? x3s_tile_stride(cfg, W) : 0;
     if ((stat_part || bnb) && part_blocks <= 0) return fail(DMC_E_INVALID, "x3s_conv: stat_blocks must be the row count of the partials");
     if (bnb) {
         a.bnb_y = bnb->y; a.bnb_stats = bnb->stats; a.bnb_gamma = bnb->gamma; a.bnb_beta = bnb->beta; a.bnb_mask = bnb->mask;
@@ -633,6 +757,7 @@ int run_x3s(const void* xs, const void* wp, const float* addend, float* y, doubl
         case 2: return launch_x3s<2, 1, 192>(a, s);
         case 3: return launch_x3s<4, 2, 608>(a, s);
         case 4: return launch_x3s<4, 1, 225>(a, s);
+        case 5: return launch_x3s<8, 2, 640, true>(a, s);
         default: return fail(DMC_E_INVALID, "x3s_conv: the patch of a %d x %d image does not fit the LDS", H, W);
     }
 }
@@ -642,16 +767,16 @@ int run_x3s(const void* xs, const void* wp, const float* addend, float* y, doubl
 // waves; the epilogue needs the waves' fp32 tiles only (no sums, no xhat tiles), which the operand LDS always covers.
 // Of the options only conv_cfg is obeyed (through x3s_choose): the measurement option conv_ablate -- bit 512 of which makes the
 // training launch take the non-staggered kernel -- is not read here, and the kernel's ablation switches get 0.
-template <int WM, int TM, int PPMAX>
+template <int WM, int TM, int PPMAX, bool ROWT = false>
 int launch_x3s_eval(const X3EvalArgs& a, hipStream_t s) {
     constexpr int BM = 32 * TM * WM;
     constexpr size_t lds_bytes = 2 * 3 * PPMAX * 32 + 2 * 3 * 3 * 64 * 32;
-    static_assert((size_t)BM * 272 <= lds_bytes, "the epilogue tiles live in the operand LDS");
-    dim3 grid((a.M + BM - 1) / BM, a.R / 64);
+    static_assert((size_t)BM * 272 <= lds_bytes && lds_bytes <= 160 * 1024, "the epilogue tiles live in the operand LDS");
+    dim3 grid((a.M + a.bms - 1) / a.bms, a.R / 64);
     static LdsLimit lim_attr;
-    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX, (WM >= 4), 1, true>), (int)lds_bytes);
+    const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<WM, 1, TM, 2, PPMAX, (WM >= 4), 1, true, ROWT>), (int)lds_bytes);
     if (attr != hipSuccess) return fail(DMC_E_LAUNCH, "x3s_conv_bn_eval: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr));
-    x3s_conv_kernel<WM, 1, TM, 2, PPMAX, (WM >= 4), 1, true><<<grid, WM * 64, lds_bytes, s>>>(a);
+    x3s_conv_kernel<WM, 1, TM, 2, PPMAX, (WM >= 4), 1, true, ROWT><<<grid, WM * 64, lds_bytes, s>>>(a);
     return check_launch("x3s_conv_bn_eval");
 }
 
@@ -937,7 +1062,8 @@ int dmc_x3s_conv_stat_blocks(int N, int H, int W, int Cout) {
     const int cfg = x3s_choose(N, H, W, Cout);
     if (cfg < 0) return 0;
     const long M = (long)N * H * W;
-    return (int)((M + X3CFGS[cfg].BM - 1) / X3CFGS[cfg].BM);
+    const int stride = x3s_tile_stride(cfg, W);              // the launches' grid (launch_x3s)
+    return (int)((M + stride - 1) / stride);
 }
 
 int dmc_x3s_conv_fwd(const void* xs, const void* wpack_f, float* y, double* stat_partials, int stat_blocks, int N, int H, int W,
@@ -963,12 +1089,15 @@ int dmc_x3s_conv_bn_eval(const void* xs, const void* wpack_f, const float* stats
     a.stats = stats; a.gamma = gamma; a.beta = beta; a.res = residual; a.ys = static_cast<unsigned short*>(ys);
     a.s2d = s2d ? 1 : 0; a.relu = relu ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    switch (x3s_choose(N, H, W, Cout)) {
+    const int cfg = x3s_choose(N, H, W, Cout);
+    a.bms = cfg >= 0 ? x3s_tile_stride(cfg, W) : 0;
+    switch (cfg) {
         case 0: return launch_x3s_eval<8, 1, 608>(a, s);
         case 1: return launch_x3s_eval<4, 1, 320>(a, s);
         case 2: return launch_x3s_eval<2, 1, 192>(a, s);
         case 3: return launch_x3s_eval<4, 2, 608>(a, s);
         case 4: return launch_x3s_eval<4, 1, 225>(a, s);
+        case 5: return launch_x3s_eval<8, 2, 640, true>(a, s);
         default: return fail(DMC_E_INVALID, "dmc_x3s_conv_bn_eval: the patch of a %d x %d image does not fit the LDS", H, W);
     }
 }
@@ -1037,6 +1166,7 @@ int dmc_x3s_conv_dgrad_s2(const void* dys, const void* wpack_t2, float* dx, int 
     a.N = N; a.H = OH; a.W = OW; a.K = Cout; a.R = Cin; a.M = N * OH * OW;
     a.plane_bytes = (unsigned)a.M * 32u;
     a.ablate = option(OPT_CONV_ABLATE);
+    a.bms = 128;
     constexpr size_t lds_bytes = 2 * 3 * 320 * 32 + 2 * 3 * 3 * 64 * 32;
     static LdsLimit lim_attr;
     const hipError_t attr = lim_attr.raise(reinterpret_cast<const void*>(&x3s_conv_kernel<4, 1, 1, 2, 320, true, 4>), (int)lds_bytes);
