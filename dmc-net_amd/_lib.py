@@ -179,6 +179,10 @@ SIGNATURES = {
     "dmc_dconv_pack_weights": (_I, [_P, _P, _I, _I, _I, _P]),
     "dmc_dconv_fwd": (_I, [_P] * 3 + [_I] * 6 + [_P]),
     "dmc_dconv_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "dmc_bnlrelu_supported": (_I, [_I, _I]),
+    "dmc_bnlrelu_scratch_bytes": (_Z, [_I, _I]),
+    "dmc_bnlrelu_fwd": (_I, [_P] * 8 + [_I, _I, _F, _F, _F, _P]),
+    "dmc_bnlrelu_bwd": (_I, [_P] * 9 + [_I, _I, _F, _P]),
 }
 
 _lib = None

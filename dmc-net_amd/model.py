@@ -12,8 +12,10 @@ estimator / discriminator variants, by default the training of the ContextNetwor
 ``nn.Linear`` heads stay on PyTorch-ROCm ops.  With ``DMC_CTX_TRAIN=1`` (``CTX_TRAIN``, off by default)
 the dilated convolutions of the ContextNetworks' five middle units -- forward, data gradient and weight
 gradient, 99.4 % of the arithmetic -- run on csrc/dconv.hip (``ops.dilated_conv``) in training as well;
-their BatchNorms, LeakyReLUs, first unit and head(s) remain the stock modules.  Passing ``arch_d``
-selects the GAN variant.
+their BatchNorms, LeakyReLUs, first unit and head(s) remain the stock modules.  ``DMC_CTX_TRAIN_BN=1``
+(``CTX_TRAIN_BN``, off by default, effective only with ``CTX_TRAIN``) also runs the BatchNorm + LeakyReLU of the first and
+the five middle units, forward and backward, on csrc/ctx_bn.hip (``ops.bn_leaky``); the 2-channel head(s) stay stock.
+Passing ``arch_d`` selects the GAN variant.
 """
 import os as _os
 
@@ -32,6 +34,10 @@ CTX_EVAL = _os.environ.get("DMC_CTX_EVAL", "1") != "0"
 #: BatchNorm2d and LeakyReLU; the first unit and the heads stay stock) whenever ops.context_train_supported accepts the network
 #: and the input.  Off by default: the stock modules, bit for bit.
 CTX_TRAIN = _os.environ.get("DMC_CTX_TRAIN", "0") == "1"
+#: DMC_CTX_TRAIN_BN=1 (read once, here; default 0; effective only together with CTX_TRAIN): on that route the BatchNorm2d + LeakyReLU
+#: of the first unit and of the five middle units run as ops.bn_leaky (csrc/ctx_bn.hip: batch statistics, apply and both backward
+#: passes, 3 + 5 passes over the activation instead of 5 + 8) wherever ops.bn_leaky_supported accepts the unit; the heads stay stock.
+CTX_TRAIN_BN = _os.environ.get("DMC_CTX_TRAIN_BN", "0") == "1"
 
 # ---------------------------------------------------------------------------- generators
 
@@ -158,7 +164,7 @@ class ContextNetwork(nn.Module):
         if CTX_EVAL and ops.context_eval_supported(self, x):
             return ops.context_eval(self, x)
         if CTX_TRAIN and ops.context_train_supported(self, x):
-            return ops.context_train(self, x, checked=True)
+            return ops.context_train(self, x, checked=True, fused_bn=CTX_TRAIN_BN)
         return self.conv_context(x)
 
 
@@ -180,7 +186,7 @@ class ContextNetworkAtt(nn.Module):
         if CTX_EVAL and ops.context_eval_supported(self, x):
             return ops.context_eval(self, x)
         if CTX_TRAIN and ops.context_train_supported(self, x):
-            return ops.context_train(self, x, checked=True)
+            return ops.context_train(self, x, checked=True, fused_bn=CTX_TRAIN_BN)
         x = self.conv_context(x)
         return self.predict_flow(x), self.predict_att(x)
 

@@ -2816,6 +2816,85 @@ def dilated_conv(x, weight, dilation):
     return _DilatedConv.apply(x, weight, int(dilation))
 
 
+# ---- ... and their BatchNorm2d + LeakyReLU in one op (csrc/ctx_bn.hip) ----
+
+def bn_leaky_supported(x, bn, act):
+    """True if ``act(bn(x))`` can run as ``bn_leaky(x, bn, act.negative_slope)``: a CUDA fp32 [N, C, H, W] ``x`` (any strides: it is
+    made channels_last), an nn.BatchNorm2d in train() with affine parameters, running statistics and a momentum, all fp32 on the
+    GPU, an nn.LeakyReLU with a slope in (0, 1), and a shape dmc_bnlrelu_supported accepts (C in {32, 64, 96, 128}, N H W >= 2,
+    N H W C < 2^31).  False on the CPU."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+        return False
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and bn.num_features == x.shape[1]):
+        return False
+    if not all(t is not None and t.is_cuda and t.dtype == torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return False
+    if not (isinstance(act, torch.nn.LeakyReLU) and 0.0 < act.negative_slope < 1.0):
+        return False
+    n, c, h, w = x.shape
+    return bool(_lib.load().dmc_bnlrelu_supported(n * h * w, c))
+
+
+class _BnLeaky(torch.autograd.Function):
+    """LeakyReLU(BatchNorm2d(x)) with batch statistics of a ContextNetwork unit (code/dmcnet/model.py:45-104) over channels_last
+    tensors.  Kept for the backward: x and the 2 C floats (mean, invstd); the slope of every element is recomputed from them."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, slope, eps, momentum):
+        _need_cuda(x, gamma, beta, running_mean, running_var)
+        lib = _lib.load()
+        if not (x.dim() == 4 and x.numel() > 0 and lib.dmc_bnlrelu_supported(x.shape[0] * x.shape[2] * x.shape[3], x.shape[1])
+                and gamma.numel() == x.shape[1] and beta.numel() == x.shape[1]):
+            raise _lib.DmcHipError("bn_leaky: x %s with %d BatchNorm channels is not served by the kernels (bn_leaky_supported)"
+                                   % (tuple(x.shape), gamma.numel()))
+        x, gamma, beta = _as_cl(x), gamma.detach().contiguous(), beta.detach().contiguous()
+        n, c, h, w = x.shape
+        m = n * h * w
+        y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device, memory_format=_CL)
+        stats = torch.empty(2 * c, dtype=torch.float32, device=x.device)
+        scratch = torch.empty(lib.dmc_bnlrelu_scratch_bytes(m, c), dtype=torch.uint8, device=x.device)
+        with _span("bn_leaky_fwd"):
+            _lib.check(lib.dmc_bnlrelu_fwd(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                           _lib.ptr(y), _lib.ptr(stats), _lib.ptr(scratch), m, c, float(slope), float(eps), float(momentum),
+                                           _stream()), "dmc_bnlrelu_fwd")
+        ctx.save_for_backward(x, gamma, beta, stats)
+        ctx.slope = float(slope)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, gamma, beta, stats = ctx.saved_tensors
+        lib = _lib.load()
+        n, c, h, w = x.shape
+        m = n * h * w
+        dy = _as_cl(dy)
+        dz = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device, memory_format=_CL)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        scratch = torch.empty(lib.dmc_bnlrelu_scratch_bytes(m, c), dtype=torch.uint8, device=x.device)
+        with _span("bn_leaky_bwd"):
+            _lib.check(lib.dmc_bnlrelu_bwd(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(stats), _lib.ptr(scratch),
+                                           _lib.ptr(dz), _lib.ptr(dgamma), _lib.ptr(dbeta), m, c, ctx.slope, _stream()), "dmc_bnlrelu_bwd")
+        need = ctx.needs_input_grad
+        return (dz if need[0] else None, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None)
+
+
+def bn_leaky(x, bn, slope):
+    """``F.leaky_relu(bn(x), slope)`` for an nn.BatchNorm2d ``bn`` in train() on the kernels of csrc/ctx_bn.hip, with autograd
+    (once differentiable).  ``x`` is a CUDA fp32 [N, C, H, W] tensor (made channels_last if it is not, and so is the gradient that
+    arrives); the result is an ordinary tensor in channels_last memory.  Updates ``bn.running_mean``, ``bn.running_var`` and
+    ``bn.num_batches_tracked`` as the module does.  A frozen weight or bias and an input that needs no gradient get None.  Shapes
+    and modules: see bn_leaky_supported.  No CPU fallback."""
+    _need_cuda(x)
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None):
+        raise _lib.DmcHipError("bn_leaky: the BatchNorm2d must be in train() with affine parameters, running statistics and a momentum "
+                               "(bn_leaky_supported)")
+    y = _BnLeaky.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(slope), bn.eps, bn.momentum)
+    bn.num_batches_tracked.add_(1)
+    return y
+
+
 def _ctx_train_plan(net):
     """(first unit, [(conv, bn, act), ...] middle units, [head modules]) of a ContextNetwork / ContextNetworkAtt with BatchNorm
     whose middle units are of the form dilated_conv serves, or None."""
@@ -2867,17 +2946,31 @@ def context_train_supported(net, x):
     return True
 
 
-def context_train(net, x, checked=False):
+def context_train(net, x, checked=False, fused_bn=False):
     """``net(x)`` of a ContextNetwork (-> gen_flow) or ContextNetworkAtt (-> (gen_flow, att_flow)) with autograd, unit by unit: the
     first unit and the head(s) as their stock modules on a channels_last input, every middle unit as ops.dilated_conv followed by
     the module's OWN BatchNorm2d and LeakyReLU (running statistics, momentum, num_batches_tracked and the in-place activation as
-    before).  Requires context_train_supported(net, x); ``checked=True``: the caller has just asked it (the modules' forward)."""
+    before).  Requires context_train_supported(net, x); ``checked=True``: the caller has just asked it (the modules' forward).
+
+    ``fused_bn=True`` (model.CTX_TRAIN_BN): the BatchNorm2d + LeakyReLU of the first unit (behind its own stock Conv2d) and of
+    every middle unit run as ops.bn_leaky wherever bn_leaky_supported accepts them; a unit it refuses (a BatchNorm in eval()
+    inside a training network) keeps its stock modules, the others are unaffected.  The heads stay stock."""
     if not checked and not context_train_supported(net, x):
         raise _lib.DmcHipError("context_train: the network or the input is not served by the kernels (context_train_supported)")
     first, middle, heads = _ctx_train_plan(net)
     with _span("context_train"):
-        t = first(_as_cl(x))
-        for conv, bn, act in middle:
-            t = act(bn(dilated_conv(t, conv.weight, conv.dilation[0])))
+        if not fused_bn:
+            t = first(_as_cl(x))
+            for conv, bn, act in middle:
+                t = act(bn(dilated_conv(t, conv.weight, conv.dilation[0])))
+        else:
+            def tail(t, bn, act):
+                return bn_leaky(t, bn, act.negative_slope) if bn_leaky_supported(t, bn, act) else act(bn(t))
+            if len(first) == 3 and isinstance(first[1], torch.nn.BatchNorm2d) and isinstance(first[2], torch.nn.LeakyReLU):
+                t = tail(first[0](_as_cl(x)), first[1], first[2])
+            else:
+                t = first(_as_cl(x))
+            for conv, bn, act in middle:
+                t = tail(dilated_conv(t, conv.weight, conv.dilation[0]), bn, act)
         outs = [h(t) for h in heads]
     return outs[0] if len(outs) == 1 else tuple(outs)

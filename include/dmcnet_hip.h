@@ -890,6 +890,30 @@ int dmc_dconv_fwd(const float* x, const void* wpack, float* y, int N, int H, int
 int dmc_dconv_wgrad(const float* x, const float* dy, float* dw_ohwi, void* workspace, int N, int H, int W, int Cin, int Cout,
                     int dilation, dmc_stream_t stream);
 
+/* ---- ContextNetwork / ContextNetworkAtt in training: BatchNorm2d + LeakyReLU (csrc/ctx_bn.hip) ----
+ * Replaces: nn.BatchNorm2d in train() (batch statistics) followed by the in-place nn.LeakyReLU of the units of
+ *           code/dmcnet/model.py:45-104, and their backward passes, over [M][C] fp32 row-major views of channels_last memory
+ *           (M = N * H * W).  The convolution in front is not part of it.
+ * dmc_bnlrelu_supported (code/dmcnet/model.py:45-104): 1 when C in {32, 64, 96, 128}, M >= 2 and M * C < 2^31, else 0.
+ * dmc_bnlrelu_scratch_bytes (code/dmcnet/model.py:45-104): the exact bytes both launching entry points use of `scratch` (fp64
+ *   per-workgroup partial sums, then 2 C floats of the backward; every byte is written before it is read); 0 when unsupported.
+ * dmc_bnlrelu_fwd (code/dmcnet/model.py:45-104): stats = (mean[C], invstd[C]) of z with invstd = (biased var + eps)^-1/2, sums
+ *   and statistics in fp64; y = t > 0 ? t : slope * t with t = fmaf((z - mean) * invstd, gamma, beta), the expression of
+ *   dmc_ctx_unit_eval.  running_mean / running_var (both or neither; may be NULL) are updated as nn.BatchNorm2d does:
+ *   r = (1 - momentum) r + momentum * (mean | var * M / (M - 1)).
+ * dmc_bnlrelu_bwd (code/dmcnet/model.py:45-104): from z, dy and the forward's stats (y is not read): t is recomputed with the
+ *   forward's expression, g = dy * (t > 0 ? 1 : slope) (t == 0 takes slope), xhat = (z - mean) * invstd;
+ *   dbeta = sum g, dgamma = sum g xhat (fp64 sums), dz = gamma invstd (g - dbeta / M - xhat dgamma / M).
+ * Deterministic, no atomics: bit-identical from run to run.  Inputs are read only.
+ * DMC_E_INVALID before any launch (nothing written): a NULL required pointer, exactly one running pointer, a shape outside
+ * dmc_bnlrelu_supported(), eps <= 0, slope outside (0, 1), momentum outside [0, 1]. */
+int dmc_bnlrelu_supported(int M, int C);
+size_t dmc_bnlrelu_scratch_bytes(int M, int C);
+int dmc_bnlrelu_fwd(const float* z, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                    float* stats, void* scratch, int M, int C, float slope, float eps, float momentum, dmc_stream_t stream);
+int dmc_bnlrelu_bwd(const float* z, const float* dy, const float* gamma, const float* beta, const float* stats, void* scratch,
+                    float* dz, float* dgamma, float* dbeta, int M, int C, float slope, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

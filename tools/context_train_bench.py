@@ -13,8 +13,10 @@ unless told otherwise.  Warm-up first, then `--iters` runs per route and pair, t
 Prints ONE JSON line: ms, TFLOP/s fp32-equivalent (2 x MACs / time; a training step counts three convolutions' worth) and the
 share of the bf16x3 bound (2,500 / 6 = 416.7 TFLOP/s), the ratio stock / ours, the two routes' agreement, and the sha256 over the
 library's source hashes; ``--table`` also prints the rows as a Markdown table.
+``--bn`` prints the BatchNorm + LeakyReLU table instead (bn_table below: ops.bn_leaky per unit width, and the whole step on the
+three routes stock / CTX_TRAIN / CTX_TRAIN + CTX_TRAIN_BN; recorded in profiles/context_train_bn_bench.json).
 
-    python tools/context_train_bench.py [--frames 24] [--size 224] [--warmup 2] [--iters 5] [--pairs 3] [--table] [--out FILE]"""
+    python tools/context_train_bench.py [--bn] [--frames 24] [--size 224] [--warmup 2] [--iters 5] [--pairs 3] [--table] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -55,6 +57,138 @@ def sources_hash():
     return hashlib.sha256(json.dumps(build.source_hashes(), sort_keys=True).encode()).hexdigest()
 
 
+HBM_ACHIEVABLE_TBS = 6.3      # MI355X: 8 TB/s peak, about 6.3 TB/s achievable
+
+
+def bn_table(args):
+    """--bn: ops.bn_leaky (csrc/ctx_bn.hip, what DMC_CTX_TRAIN_BN=1 adds to the DMC_CTX_TRAIN=1 route) against the stock
+    BatchNorm2d + in-place LeakyReLU.
+      * per unit width: forward and backward through the C ABI on [M][C] tensors against the stock modules on channels_last tensors
+        (the backward as torch.autograd.grad of their graph), bytes from the shapes (3 M C 4 forward, 5 M C 4 backward) as TB/s;
+      * the whole training step of both networks on three routes in one process: stock, CTX_TRAIN, CTX_TRAIN + CTX_TRAIN_BN; every
+        pair's times are kept, the order rotates from pair to pair."""
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("context_train_bench: needs a GPU (no CPU timing)")
+    from dmcnet_amd import _lib, model, ops
+    from oracle import dmc_oracle as O
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    CL = torch.channels_last
+    n, h, w = args.frames, args.size, args.size
+    M = n * h * w
+    g = torch.Generator(device=dev).manual_seed(24 + n)
+    s = ops._stream()
+    slope, eps, mom = 0.1, 1e-5, 0.1
+    units, steps = [], []
+
+    def rel(a, b):
+        return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
+
+    net0 = O.seeded_state_fill(model.ContextNetwork(5, True, 0), seed=26).to(dev).train()
+    widths = {}
+    for i, unit in list(enumerate(net0.conv_context))[:6]:
+        widths.setdefault(unit[1].num_features, []).append(i)
+    for c, where in sorted(widths.items()):
+        bn = net0.conv_context[where[0]][1]
+        act = torch.nn.LeakyReLU(slope, inplace=True)
+        z = torch.randn((n, c, h, w), generator=g, device=dev).contiguous(memory_format=CL)
+        dy = torch.randn((n, c, h, w), generator=g, device=dev).contiguous(memory_format=CL)
+        gamma, beta = bn.weight.detach(), bn.bias.detach()
+        rm, rv = bn.running_mean.clone(), bn.running_var.clone()
+        y, dz = torch.empty_like(z), torch.empty_like(z)
+        stats, dgamma, dbeta = torch.empty(2 * c, device=dev), torch.empty(c, device=dev), torch.empty(c, device=dev)
+        scratch = torch.empty(lib.dmc_bnlrelu_scratch_bytes(M, c), dtype=torch.uint8, device=dev)
+
+        def ours_fwd():
+            _lib.check(lib.dmc_bnlrelu_fwd(_lib.ptr(z), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(y), _lib.ptr(stats),
+                                           _lib.ptr(scratch), M, c, slope, eps, mom, s), "dmc_bnlrelu_fwd")
+            return y
+
+        def ours_bwd():
+            _lib.check(lib.dmc_bnlrelu_bwd(_lib.ptr(z), _lib.ptr(dy), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(stats), _lib.ptr(scratch), _lib.ptr(dz),
+                                           _lib.ptr(dgamma), _lib.ptr(dbeta), M, c, slope, s), "dmc_bnlrelu_bwd")
+            return dz
+
+        with torch.no_grad():
+            best_f, last_f = alternate(ours_fwd, lambda: act(bn(z)), args.warmup, args.iters, args.pairs)
+        agree_f = rel(last_f["ours"], last_f["stock"])
+        del last_f
+        zs = z.clone().requires_grad_(True)
+        ys = act(bn(zs))                                           # the graph the stock gradients are taken from
+        best_b, last_b = alternate(ours_bwd, lambda: torch.autograd.grad(ys, (zs, bn.weight, bn.bias), dy, retain_graph=True)[0],
+                                   args.warmup, args.iters, args.pairs)
+        agree_b = rel(last_b["ours"], last_b["stock"])
+        for what, best, nbytes, agree in (("forward", best_f, 3.0 * M * c * 4, agree_f), ("backward", best_b, 5.0 * M * c * 4, agree_b)):
+            tbs = nbytes / best["ours"] / 1e9
+            units.append({"units": where, "channels": c, "rows": M, "pass": what, "ours_ms": round(best["ours"], 4), "stock_ms": round(best["stock"], 4),
+                          "stock_over_ours": round(best["stock"] / best["ours"], 3), "mbytes": round(nbytes / 1e6, 1), "ours_tbs": round(tbs, 3),
+                          "ours_share_of_achievable": round(tbs / HBM_ACHIEVABLE_TBS, 3), "rel_err_ours_vs_stock": agree})
+            print("# C=%d %s: ours %.3f ms (%.2f TB/s), stock %.3f ms" % (c, what, best["ours"], tbs, best["stock"]), file=sys.stderr, flush=True)
+        del z, dy, y, dz, zs, ys, last_b, scratch
+        torch.cuda.empty_cache()
+
+    routes = (("stock", False, False), ("ctx_train", True, False), ("ctx_train_bn", True, True))
+    for att in [int(a) for a in args.nets.split(",") if a != ""]:
+        cls = model.ContextNetworkAtt if att else model.ContextNetwork
+        net = O.seeded_state_fill(cls(5, True, 0), seed=26).to(dev).train()
+        x = torch.randn((n, 5, h, w), generator=g, device=dev)
+        r = torch.randn((n, 2, h, w), generator=g, device=dev)
+
+        def step(train, bn_on):
+            model.CTX_TRAIN, model.CTX_TRAIN_BN = train, bn_on
+            try:
+                for p in net.parameters():
+                    p.grad = None
+                xi = x.clone().requires_grad_(True)
+                out = net(xi)
+                outs = out if isinstance(out, tuple) else (out,)
+                sum((t * r).sum() for t in outs).backward()
+            finally:
+                model.CTX_TRAIN, model.CTX_TRAIN_BN = False, False
+            return torch.cat([xi.grad.reshape(-1)] + [p.grad.reshape(-1) for p in net.parameters()])
+
+        for _ in range(args.warmup):
+            for _, a, b in routes:
+                step(a, b)
+        per_pair, last = [], {}
+        for p in range(args.pairs):
+            order = routes[p % 3:] + routes[:p % 3]
+            ms = {}
+            for name, a, b in order:
+                ms[name], last[name] = timed(lambda: step(a, b), args.iters)
+            per_pair.append({k: round(v, 3) for k, v in ms.items()})
+        res = {"network": cls.__name__, "frames": n, "pairs": per_pair,
+               "best_ms": {name: min(p[name] for p in per_pair) for name, _, _ in routes},
+               "bn_faster_than_ctx_train_in_every_pair": all(p["ctx_train_bn"] < p["ctx_train"] for p in per_pair),
+               "rel_err_bn_vs_stock": rel(last["ctx_train_bn"], last["stock"]), "rel_err_ctx_train_vs_stock": rel(last["ctx_train"], last["stock"])}
+        steps.append(res)
+        print("# %s: %s" % (cls.__name__, per_pair), file=sys.stderr, flush=True)
+        del x, r, last, net
+        torch.cuda.empty_cache()
+
+    res = {"tool": "context_train_bench --bn", "device": torch.cuda.get_device_name(0), "size": args.size, "frames": n,
+           "hbm_achievable_tbs": HBM_ACHIEVABLE_TBS, "warmup": args.warmup, "iters": args.iters, "pairs": args.pairs,
+           "sources_sha256": sources_hash(), "units": units, "steps": steps}
+    line = json.dumps(res, sort_keys=True)
+    print(line, flush=True)
+    if args.table:
+        print("| units | C | pass | MB | ours ms | stock ms | stock / ours | ours TB/s | of %.1f | ours vs stock |" % HBM_ACHIEVABLE_TBS)
+        print("|---|---|---|---|---|---|---|---|---|---|")
+        for u in units:
+            print("| %s | %d | %s | %.0f | %.3f | %.3f | %.2f | %.2f | %.0f %% | %.1e |" % (
+                ",".join(map(str, u["units"])), u["channels"], u["pass"], u["mbytes"], u["ours_ms"], u["stock_ms"], u["stock_over_ours"], u["ours_tbs"],
+                100 * u["ours_share_of_achievable"], u["rel_err_ours_vs_stock"]))
+        print("| network | pair | stock ms | CTX_TRAIN ms | CTX_TRAIN + CTX_TRAIN_BN ms |")
+        print("|---|---|---|---|---|")
+        for st in steps:
+            for i, p in enumerate(st["pairs"]):
+                print("| %s | %d | %.2f | %.2f | %.2f |" % (st["network"], i + 1, p["stock"], p["ctx_train"], p["ctx_train_bn"]))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=24)
@@ -65,7 +199,10 @@ def main():
     ap.add_argument("--nets", default="0,1", help="att values of the whole-network rows: 0 = ContextNetwork, 1 = ContextNetworkAtt")
     ap.add_argument("--table", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bn", action="store_true", help="the BatchNorm + LeakyReLU table (ops.bn_leaky, CTX_TRAIN_BN) instead of the convolutions'")
     args = ap.parse_args()
+    if args.bn:
+        return bn_table(args)
 
     import torch
     import torch.nn.functional as F
