@@ -183,6 +183,17 @@ SIGNATURES = {
     "dmc_bnlrelu_scratch_bytes": (_Z, [_I, _I]),
     "dmc_bnlrelu_fwd": (_I, [_P] * 8 + [_I, _I, _F, _F, _F, _P]),
     "dmc_bnlrelu_bwd": (_I, [_P] * 9 + [_I, _I, _F, _P]),
+    "dmc_ctxends_supported": (_I, [_I] * 3),
+    "dmc_ctxends_wgrad_workspace_bytes": (_Z, [_I] * 4),
+    "dmc_ctxends_bn_scratch_bytes": (_Z, [_I] * 3),
+    "dmc_ctxends_first_fwd": (_I, [_P] * 3 + [_I] * 3 + [_P]),
+    "dmc_ctxends_first_dgrad": (_I, [_P] * 3 + [_I] * 3 + [_P]),
+    "dmc_ctxends_first_wgrad": (_I, [_P] * 4 + [_I] * 3 + [_P]),
+    "dmc_ctxends_heads_fwd": (_I, [_P] * 5 + [_I] * 3 + [_P]),
+    "dmc_ctxends_heads_dgrad": (_I, [_P] * 5 + [_I] * 3 + [_P]),
+    "dmc_ctxends_heads_wgrad": (_I, [_P] * 6 + [_I] * 3 + [_P]),
+    "dmc_ctxends_bn_fwd": (_I, [_P] * 8 + [_I] * 3 + [_F, _F, _F, _I, _P]),
+    "dmc_ctxends_bn_bwd": (_I, [_P] * 9 + [_I] * 3 + [_F, _I, _P]),
 }
 
 _lib = None

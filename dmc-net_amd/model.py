@@ -15,6 +15,9 @@ gradient, 99.4 % of the arithmetic -- run on csrc/dconv.hip (``ops.dilated_conv`
 their BatchNorms, LeakyReLUs, first unit and head(s) remain the stock modules.  ``DMC_CTX_TRAIN_BN=1``
 (``CTX_TRAIN_BN``, off by default, effective only with ``CTX_TRAIN``) also runs the BatchNorm + LeakyReLU of the first and
 the five middle units, forward and backward, on csrc/ctx_bn.hip (``ops.bn_leaky``); the 2-channel head(s) stay stock.
+``DMC_CTX_TRAIN_ENDS=1`` (``CTX_TRAIN_ENDS``, off by default, effective only with ``CTX_TRAIN``) moves the two ends onto
+csrc/ctx_ends.hip as well: the first unit's 5 -> 32 convolution (``ops.ctx_first_conv``), the heads' 32 -> 2 convolutions
+(``ops.ctx_head_convs``) and, together with ``CTX_TRAIN_BN``, the heads' BatchNorm + LeakyReLU (``ops.bn_leaky_planes``).
 Passing ``arch_d`` selects the GAN variant.
 """
 import os as _os
@@ -38,6 +41,12 @@ CTX_TRAIN = _os.environ.get("DMC_CTX_TRAIN", "0") == "1"
 #: of the first unit and of the five middle units run as ops.bn_leaky (csrc/ctx_bn.hip: batch statistics, apply and both backward
 #: passes, 3 + 5 passes over the activation instead of 5 + 8) wherever ops.bn_leaky_supported accepts the unit; the heads stay stock.
 CTX_TRAIN_BN = _os.environ.get("DMC_CTX_TRAIN_BN", "0") == "1"
+#: DMC_CTX_TRAIN_ENDS=1 (read once, here; default 0; effective only together with CTX_TRAIN): on that route the first unit's 5 -> 32
+#: convolution runs as ops.ctx_first_conv and the heads' 32 -> 2 convolutions as one ops.ctx_head_convs call (csrc/ctx_ends.hip:
+#: forward, data gradient -- both heads summed in one launch -- and weight gradient); with CTX_TRAIN_BN as well the heads'
+#: BatchNorm2d + LeakyReLU (+ ReLU) run as ops.bn_leaky_planes.  With all three flags no convolution and no BatchNorm of a
+#: ContextNetwork training step is a stock module.
+CTX_TRAIN_ENDS = _os.environ.get("DMC_CTX_TRAIN_ENDS", "0") == "1"
 
 # ---------------------------------------------------------------------------- generators
 
@@ -164,7 +173,7 @@ class ContextNetwork(nn.Module):
         if CTX_EVAL and ops.context_eval_supported(self, x):
             return ops.context_eval(self, x)
         if CTX_TRAIN and ops.context_train_supported(self, x):
-            return ops.context_train(self, x, checked=True, fused_bn=CTX_TRAIN_BN)
+            return ops.context_train(self, x, checked=True, fused_bn=CTX_TRAIN_BN, own_ends=CTX_TRAIN_ENDS)
         return self.conv_context(x)
 
 
@@ -186,7 +195,7 @@ class ContextNetworkAtt(nn.Module):
         if CTX_EVAL and ops.context_eval_supported(self, x):
             return ops.context_eval(self, x)
         if CTX_TRAIN and ops.context_train_supported(self, x):
-            return ops.context_train(self, x, checked=True, fused_bn=CTX_TRAIN_BN)
+            return ops.context_train(self, x, checked=True, fused_bn=CTX_TRAIN_BN, own_ends=CTX_TRAIN_ENDS)
         x = self.conv_context(x)
         return self.predict_flow(x), self.predict_att(x)
 

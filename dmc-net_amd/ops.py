@@ -2895,6 +2895,236 @@ def bn_leaky(x, bn, slope):
     return y
 
 
+# ---- ... and the two ends: the first unit's 5 -> 32 convolution, the heads' 32 -> 2 convolutions and their BatchNorm (csrc/ctx_ends.hip) ----
+
+def _ends_geom_ok(x, c):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == c and x.numel() > 0):
+        return False
+    n, _, h, w = x.shape
+    return bool(_lib.load().dmc_ctxends_supported(n, h, w))
+
+
+def _ends_conv_ok(conv, cin, cout):
+    return (_dconv_module_ok(conv) and conv.dilation[0] == 1 and conv.in_channels == cin and conv.out_channels == cout)
+
+
+def ctx_first_conv_supported(x, conv):
+    """True if ``conv(x)`` can run as ``ctx_first_conv(x, conv.weight)``: a Conv2d(5, 32, 3, 1, 1, 1, bias=False) with fp32 CUDA
+    weights (the first unit of code/dmcnet/model.py:45-104), a CUDA fp32 [N, 5, H, W] input and N H W 128 < 2^31
+    (dmc_ctxends_supported).  False on the CPU."""
+    return _ends_conv_ok(conv, 5, 32) and _ends_geom_ok(x, 5)
+
+
+def _like_weight(dw, weight):
+    """dw in the strides of ``weight``."""
+    return dw if dw.stride() == weight.stride() else torch.empty_like(weight).copy_(dw)
+
+
+class _CtxFirstConv(torch.autograd.Function):
+    """Conv2d(5, 32, 3, 1, 1, 1, bias=False) of the first ContextNetwork unit (code/dmcnet/model.py:45-104): NCHW planes in,
+    channels_last out; forward, data gradient and weight gradient on csrc/ctx_ends.hip."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        _need_cuda(x, weight)
+        if not (weight.dim() == 4 and tuple(weight.shape) == (32, 5, 3, 3) and _ends_geom_ok(x, 5)):
+            raise _lib.DmcHipError("ctx_first_conv: x %s, weight %s is not served by the kernels (ctx_first_conv_supported)"
+                                   % (tuple(x.shape), tuple(weight.shape)))
+        lib = _lib.load()
+        x = x.contiguous()
+        n, _, h, w = x.shape
+        with _span("ctx_first_fwd"):
+            y = torch.empty((n, 32, h, w), dtype=torch.float32, device=x.device, memory_format=_CL)
+            _lib.check(lib.dmc_ctxends_first_fwd(_lib.ptr(x), _lib.ptr(weight.detach().contiguous()), _lib.ptr(y), n, h, w, _stream()),
+                       "dmc_ctxends_first_fwd")
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        lib = _lib.load()
+        n, _, h, w = x.shape
+        dy = _as_cl(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            with _span("ctx_first_dgrad"):
+                dx = torch.empty((n, 5, h, w), dtype=torch.float32, device=x.device)
+                _lib.check(lib.dmc_ctxends_first_dgrad(_lib.ptr(dy), _lib.ptr(weight.detach().contiguous()), _lib.ptr(dx), n, h, w, _stream()),
+                           "dmc_ctxends_first_dgrad")
+        if ctx.needs_input_grad[1]:
+            with _span("ctx_first_wgrad"):
+                dwc = torch.empty((32, 5, 3, 3), dtype=torch.float32, device=x.device)
+                work = torch.empty(lib.dmc_ctxends_wgrad_workspace_bytes(n, h, w, 5), dtype=torch.uint8, device=x.device)
+                _lib.check(lib.dmc_ctxends_first_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dwc), _lib.ptr(work), n, h, w, _stream()),
+                           "dmc_ctxends_first_wgrad")
+                dw = _like_weight(dwc, weight)
+        return dx, dw
+
+
+def ctx_first_conv(x, weight):
+    """``F.conv2d(x, weight, None, 1, 1, 1)`` for the first ContextNetwork unit's ``weight`` [32, 5, 3, 3] on the kernels of
+    csrc/ctx_ends.hip, with autograd (once differentiable).  ``x`` is a CUDA fp32 [N, 5, H, W] tensor (made contiguous if it is not);
+    the result is an ordinary [N, 32, H, W] tensor in channels_last memory.  A frozen weight launches no weight gradient, an input
+    that needs no gradient no data gradient; the weight gradient has the weight's strides.  No CPU fallback."""
+    return _CtxFirstConv.apply(x, weight)
+
+
+def ctx_head_convs_supported(t, convs):
+    """True if ``[conv(t) for conv in convs]`` can run as ``ctx_head_convs(t, [conv.weight for conv in convs])``: one or two
+    Conv2d(32, 2, 3, 1, 1, 1, bias=False) with fp32 CUDA weights (predict_flow / predict_att of code/dmcnet/model.py:45-104), a CUDA
+    fp32 [N, 32, H, W] input and N H W 128 < 2^31.  False on the CPU."""
+    convs = list(convs)
+    return 1 <= len(convs) <= 2 and all(_ends_conv_ok(c, 32, 2) for c in convs) and _ends_geom_ok(t, 32)
+
+
+class _CtxHeadConvs(torch.autograd.Function):
+    """The Conv2d(32, 2, 3, 1, 1, 1, bias=False) of one or two ContextNetwork heads over the same trunk activation
+    (code/dmcnet/model.py:45-104): channels_last in, NCHW planes out, each pass one launch that reads the trunk tensor once; the
+    data gradient is the sum over the heads."""
+
+    @staticmethod
+    def forward(ctx, t, *weights):
+        _need_cuda(t, *weights)
+        if not (1 <= len(weights) <= 2 and all(w.dim() == 4 and tuple(w.shape) == (2, 32, 3, 3) for w in weights) and _ends_geom_ok(t, 32)):
+            raise _lib.DmcHipError("ctx_head_convs: t %s with weights %s is not served by the kernels (ctx_head_convs_supported)"
+                                   % (tuple(t.shape), [tuple(w.shape) for w in weights]))
+        ctx.set_materialize_grads(False)
+        lib = _lib.load()
+        t = _as_cl(t)
+        n, _, h, w = t.shape
+        ws = [_as_cl(wt.detach()) for wt in weights] + [None]
+        with _span("ctx_heads_fwd"):
+            outs = [torch.empty((n, 2, h, w), dtype=torch.float32, device=t.device) for _ in weights] + [None]
+            _lib.check(lib.dmc_ctxends_heads_fwd(_lib.ptr(t), _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(outs[0]), _lib.ptr(outs[1]), n, h, w,
+                                                 _stream()), "dmc_ctxends_heads_fwd")
+        ctx.save_for_backward(t, *weights)
+        return tuple(outs[:len(weights)])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dzs):
+        t, weights = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        lib = _lib.load()
+        n, _, h, w = t.shape
+        k = len(weights)
+        dzs = [d.contiguous() if d is not None else None for d in dzs]
+        dt, dws = None, [None] * k
+        if all(d is None for d in dzs):
+            return (None,) * (1 + k)
+        if ctx.needs_input_grad[0]:
+            with _span("ctx_heads_dgrad"):
+                ws = [_as_cl(wt.detach()) for wt in weights]
+                if k == 1:
+                    dzs2, ws2 = [dzs[0], None], [ws[0], None]
+                elif dzs[0] is None:        # the flow slot is the head that has a gradient
+                    dzs2, ws2 = [dzs[1], None], [ws[1], None]
+                else:
+                    dzs2, ws2 = dzs, ws
+                dt = torch.empty((n, 32, h, w), dtype=torch.float32, device=t.device, memory_format=_CL)
+                _lib.check(lib.dmc_ctxends_heads_dgrad(_lib.ptr(dzs2[0]), _lib.ptr(dzs2[1]), _lib.ptr(ws2[0]), _lib.ptr(ws2[1]), _lib.ptr(dt),
+                                                       n, h, w, _stream()), "dmc_ctxends_heads_dgrad")
+        live = [i for i in range(k) if ctx.needs_input_grad[1 + i] and dzs[i] is not None]
+        if live:
+            with _span("ctx_heads_wgrad"):
+                dwcl = [torch.empty((2, 32, 3, 3), dtype=torch.float32, device=t.device, memory_format=_CL) for _ in live]
+                work = torch.empty(lib.dmc_ctxends_wgrad_workspace_bytes(n, h, w, 2 * len(live)), dtype=torch.uint8, device=t.device)
+                dz2 = [dzs[i] for i in live] + [None]
+                dw2 = dwcl + [None]
+                _lib.check(lib.dmc_ctxends_heads_wgrad(_lib.ptr(t), _lib.ptr(dz2[0]), _lib.ptr(dz2[1]), _lib.ptr(dw2[0]), _lib.ptr(dw2[1]),
+                                                       _lib.ptr(work), n, h, w, _stream()), "dmc_ctxends_heads_wgrad")
+                for i, d in zip(live, dwcl):
+                    dws[i] = _like_weight(d, weights[i])
+        return (dt,) + tuple(dws)
+
+
+def ctx_head_convs(t, weights):
+    """``tuple(F.conv2d(t, w, None, 1, 1, 1) for w in weights)`` for one or two head weights [2, 32, 3, 3] on the kernels of
+    csrc/ctx_ends.hip, with autograd (once differentiable).  ``t`` is a CUDA fp32 [N, 32, H, W] tensor (made channels_last if it is
+    not); the results are contiguous [N, 2, H, W] tensors.  Every pass is one launch over both heads; the data gradient is the
+    sum of the heads' (a head whose output got no gradient is left out).  A frozen weight launches no weight gradient for it, an
+    input that needs no gradient no data gradient; weight gradients have the weights' strides.  No CPU fallback."""
+    return _CtxHeadConvs.apply(t, *weights)
+
+
+def bn_leaky_planes_supported(z, bn, act, relu=None):
+    """True if ``act(bn(z))`` (followed by ``relu``, an nn.ReLU, when given) can run as ``bn_leaky_planes(z, bn, act.negative_slope,
+    relu is not None)``: a CUDA fp32 [N, 2, H, W] ``z``, an nn.BatchNorm2d(2) in train() with affine parameters, running statistics
+    and a momentum, all fp32 on the GPU, an nn.LeakyReLU with a slope in (0, 1), N H W >= 2 and N H W 128 < 2^31.  False on the CPU."""
+    if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 4 and z.shape[1] == 2 and z.numel() > 0):
+        return False
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and bn.num_features == 2):
+        return False
+    if not all(t is not None and t.is_cuda and t.dtype == torch.float32 for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return False
+    if not (isinstance(act, torch.nn.LeakyReLU) and 0.0 < act.negative_slope < 1.0):
+        return False
+    if relu is not None and not isinstance(relu, torch.nn.ReLU):
+        return False
+    n, _, h, w = z.shape
+    return _lib.load().dmc_ctxends_bn_scratch_bytes(n, h, w) > 0
+
+
+class _BnLeakyPlanes(torch.autograd.Function):
+    """[ReLU(]LeakyReLU(BatchNorm2d(z))[)] with batch statistics of a ContextNetwork head (code/dmcnet/model.py:45-104) over
+    contiguous [N, 2, H, W] planes.  Kept for the backward: z and the 4 floats (mean, invstd)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, running_mean, running_var, slope, eps, momentum, relu):
+        _need_cuda(z, gamma, beta, running_mean, running_var)
+        lib = _lib.load()
+        if not (z.dim() == 4 and z.shape[1] == 2 and z.numel() > 0 and gamma.numel() == 2 and beta.numel() == 2
+                and lib.dmc_ctxends_bn_scratch_bytes(z.shape[0], z.shape[2], z.shape[3]) > 0):
+            raise _lib.DmcHipError("bn_leaky_planes: z %s with %d BatchNorm channels is not served by the kernels (bn_leaky_planes_supported)"
+                                   % (tuple(z.shape), gamma.numel()))
+        z, gamma, beta = z.contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
+        n, _, h, w = z.shape
+        y = torch.empty_like(z)
+        stats = torch.empty(4, dtype=torch.float32, device=z.device)
+        scratch = torch.empty(lib.dmc_ctxends_bn_scratch_bytes(n, h, w), dtype=torch.uint8, device=z.device)
+        with _span("bn_leaky_planes_fwd"):
+            _lib.check(lib.dmc_ctxends_bn_fwd(_lib.ptr(z), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                              _lib.ptr(y), _lib.ptr(stats), _lib.ptr(scratch), n, h, w, float(slope), float(eps),
+                                              float(momentum), int(bool(relu)), _stream()), "dmc_ctxends_bn_fwd")
+        ctx.save_for_backward(z, gamma, beta, stats)
+        ctx.slope, ctx.relu = float(slope), int(bool(relu))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        z, gamma, beta, stats = ctx.saved_tensors
+        lib = _lib.load()
+        n, _, h, w = z.shape
+        dy = dy.contiguous()
+        dz = torch.empty_like(z)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        scratch = torch.empty(lib.dmc_ctxends_bn_scratch_bytes(n, h, w), dtype=torch.uint8, device=z.device)
+        with _span("bn_leaky_planes_bwd"):
+            _lib.check(lib.dmc_ctxends_bn_bwd(_lib.ptr(z), _lib.ptr(dy), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(stats), _lib.ptr(scratch),
+                                              _lib.ptr(dz), _lib.ptr(dgamma), _lib.ptr(dbeta), n, h, w, ctx.slope, ctx.relu, _stream()),
+                       "dmc_ctxends_bn_bwd")
+        need = ctx.needs_input_grad
+        return (dz if need[0] else None, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None, None)
+
+
+def bn_leaky_planes(z, bn, slope, relu=False):
+    """``F.leaky_relu(bn(z), slope)`` -- and ``F.relu`` of that with ``relu=True`` -- for an nn.BatchNorm2d(2) ``bn`` in train() on the
+    kernels of csrc/ctx_ends.hip, with autograd (once differentiable).  ``z`` is a CUDA fp32 [N, 2, H, W] tensor (made contiguous
+    if it is not, and so is the gradient that arrives); the result is contiguous.  Updates ``bn.running_mean``, ``bn.running_var``
+    and ``bn.num_batches_tracked`` as the module does.  A frozen weight or bias and an input that needs no gradient get None.
+    Shapes and modules: see bn_leaky_planes_supported.  No CPU fallback."""
+    _need_cuda(z)
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None):
+        raise _lib.DmcHipError("bn_leaky_planes: the BatchNorm2d must be in train() with affine parameters, running statistics and a "
+                               "momentum (bn_leaky_planes_supported)")
+    y = _BnLeakyPlanes.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(slope), bn.eps, bn.momentum, bool(relu))
+    bn.num_batches_tracked.add_(1)
+    return y
+
+
 def _ctx_train_plan(net):
     """(first unit, [(conv, bn, act), ...] middle units, [head modules]) of a ContextNetwork / ContextNetworkAtt with BatchNorm
     whose middle units are of the form dilated_conv serves, or None."""
@@ -2946,7 +3176,39 @@ def context_train_supported(net, x):
     return True
 
 
-def context_train(net, x, checked=False, fused_bn=False):
+def _ctx_head_parts(head):
+    """(unit, relu | None) of a head: the unit itself, or Sequential(unit, nn.ReLU) (predict_att)."""
+    if (isinstance(head, torch.nn.Sequential) and len(head) == 2 and isinstance(head[0], torch.nn.Sequential)
+            and isinstance(head[1], torch.nn.ReLU)):
+        return head[0], head[1]
+    return head, None
+
+
+def _ctx_heads_own(heads, t, fused_bn):
+    """The heads on ops.ctx_head_convs (one call over every head whose convolution it serves) and, with ``fused_bn``, their
+    BatchNorm + LeakyReLU (+ ReLU) on ops.bn_leaky_planes; whatever is of another form keeps its stock modules."""
+    parts = [_ctx_head_parts(h) for h in heads]
+    own = [i for i, (u, _) in enumerate(parts) if isinstance(u, torch.nn.Sequential) and len(u) >= 1 and _ends_conv_ok(u[0], 32, 2)]
+    if not own or len(own) > 2 or not _ends_geom_ok(t, 32):
+        return [h(t) for h in heads]
+    zs = dict(zip(own, ctx_head_convs(t, [parts[i][0][0].weight for i in own])))
+    outs = []
+    for i, h in enumerate(heads):
+        if i not in zs:
+            outs.append(h(t))
+            continue
+        unit, relu = parts[i]
+        z = zs[i]
+        if fused_bn and len(unit) == 3 and bn_leaky_planes_supported(z, unit[1], unit[2], relu):
+            outs.append(bn_leaky_planes(z, unit[1], unit[2].negative_slope, relu is not None))
+            continue
+        for m in list(unit)[1:]:
+            z = m(z)
+        outs.append(relu(z) if relu is not None else z)
+    return outs
+
+
+def context_train(net, x, checked=False, fused_bn=False, own_ends=False):
     """``net(x)`` of a ContextNetwork (-> gen_flow) or ContextNetworkAtt (-> (gen_flow, att_flow)) with autograd, unit by unit: the
     first unit and the head(s) as their stock modules on a channels_last input, every middle unit as ops.dilated_conv followed by
     the module's OWN BatchNorm2d and LeakyReLU (running statistics, momentum, num_batches_tracked and the in-place activation as
@@ -2954,23 +3216,31 @@ def context_train(net, x, checked=False, fused_bn=False):
 
     ``fused_bn=True`` (model.CTX_TRAIN_BN): the BatchNorm2d + LeakyReLU of the first unit (behind its own stock Conv2d) and of
     every middle unit run as ops.bn_leaky wherever bn_leaky_supported accepts them; a unit it refuses (a BatchNorm in eval()
-    inside a training network) keeps its stock modules, the others are unaffected.  The heads stay stock."""
+    inside a training network) keeps its stock modules, the others are unaffected.  The heads stay stock.
+
+    ``own_ends=True`` (model.CTX_TRAIN_ENDS): the first unit's Conv2d(5, 32, 3, 1, 1, 1, bias=False) runs as ops.ctx_first_conv and
+    the heads' Conv2d(32, 2, 3, 1, 1, 1, bias=False) as one ops.ctx_head_convs call (csrc/ctx_ends.hip); together with
+    ``fused_bn`` each head's BatchNorm2d + LeakyReLU (+ the attention head's ReLU) runs as ops.bn_leaky_planes where
+    bn_leaky_planes_supported accepts it (a head it refuses keeps its stock modules behind our convolution).  A first unit or a
+    head of another form keeps its stock module.  ``own_ends=False``: exactly the route described above."""
     if not checked and not context_train_supported(net, x):
         raise _lib.DmcHipError("context_train: the network or the input is not served by the kernels (context_train_supported)")
     first, middle, heads = _ctx_train_plan(net)
     with _span("context_train"):
-        if not fused_bn:
-            t = first(_as_cl(x))
-            for conv, bn, act in middle:
-                t = act(bn(dilated_conv(t, conv.weight, conv.dilation[0])))
-        else:
-            def tail(t, bn, act):
-                return bn_leaky(t, bn, act.negative_slope) if bn_leaky_supported(t, bn, act) else act(bn(t))
+        def tail(t, bn, act):
+            return bn_leaky(t, bn, act.negative_slope) if fused_bn and bn_leaky_supported(t, bn, act) else act(bn(t))
+        if own_ends and ctx_first_conv_supported(x, first[0]):
+            t = ctx_first_conv(x, first[0].weight)
             if len(first) == 3 and isinstance(first[1], torch.nn.BatchNorm2d) and isinstance(first[2], torch.nn.LeakyReLU):
-                t = tail(first[0](_as_cl(x)), first[1], first[2])
+                t = tail(t, first[1], first[2])
             else:
-                t = first(_as_cl(x))
-            for conv, bn, act in middle:
-                t = tail(dilated_conv(t, conv.weight, conv.dilation[0]), bn, act)
-        outs = [h(t) for h in heads]
+                for m in list(first)[1:]:
+                    t = m(t)
+        elif fused_bn and len(first) == 3 and isinstance(first[1], torch.nn.BatchNorm2d) and isinstance(first[2], torch.nn.LeakyReLU):
+            t = tail(first[0](_as_cl(x)), first[1], first[2])
+        else:
+            t = first(_as_cl(x))
+        for conv, bn, act in middle:
+            t = tail(dilated_conv(t, conv.weight, conv.dilation[0]), bn, act)
+        outs = _ctx_heads_own(heads, t, fused_bn) if own_ends else [h(t) for h in heads]
     return outs[0] if len(outs) == 1 else tuple(outs)

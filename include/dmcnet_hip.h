@@ -914,6 +914,63 @@ int dmc_bnlrelu_fwd(const float* z, const float* gamma, const float* beta, float
 int dmc_bnlrelu_bwd(const float* z, const float* dy, const float* gamma, const float* beta, const float* stats, void* scratch,
                     float* dz, float* dgamma, float* dbeta, int M, int C, float slope, dmc_stream_t stream);
 
+/* ---- ContextNetwork / ContextNetworkAtt in training: the first unit's convolution and the head(s) (csrc/ctx_ends.hip) ----
+ * Replaces: Conv2d(5, 32, 3, 1, 1, 1, bias=False) of the first unit, Conv2d(32, 2, 3, 1, 1, 1, bias=False) of predict_flow and
+ *           predict_att and the heads' nn.BatchNorm2d(2) in train() + nn.LeakyReLU (+ nn.ReLU behind predict_att) of
+ *           code/dmcnet/model.py:45-104 -- forward, data gradient, weight gradient -- in plain fp32 FMAs.
+ * Layouts: x, dx NCHW [N][5][H][W]; the first unit's output z and its gradient dz, the trunk activation t and its gradient dt
+ *   NHWC [N][H][W][32]; a head's convolution output and its gradient NCHW [N][2][H][W]; w_first OIHW [32][5][3][3]; a head's
+ *   weight OHWI [2][3][3][32] (the layouts of dmc_ctx_first_eval / dmc_ctx_heads_eval).  o(t) = (t / 3 - 1, t % 3 - 1); a tap
+ *   outside the H x W frame contributes 0.
+ * dmc_ctxends_supported (code/dmcnet/model.py:45-104): 1 when N, H, W > 0 and N * H * W * 128 < 2^31, else 0.
+ * dmc_ctxends_wgrad_workspace_bytes (code/dmcnet/model.py:45-104): the exact bytes a weight gradient over `planes` planes uses
+ *   of `workspace` (5: dmc_ctxends_first_wgrad; 2 per head that has a gradient: dmc_ctxends_heads_wgrad): per-range partial
+ *   sums, every byte written before it is read; 0 for an unsupported shape or another plane count.
+ * dmc_ctxends_bn_scratch_bytes (code/dmcnet/model.py:45-104): the exact bytes dmc_ctxends_bn_fwd / _bwd use of `scratch` (fp64
+ *   per-workgroup partial sums, then 4 floats of the backward); 0 when unsupported or N * H * W < 2.
+ * dmc_ctxends_first_fwd (code/dmcnet/model.py:45-104): z[p][co] = sum_{ci,t} x[ci][p + o(t)] w[co][ci][t], summed over
+ *   (ci, ky, kx) in that order with fmaf: the sum of dmc_ctx_first_eval, bit for bit.
+ * dmc_ctxends_first_dgrad (code/dmcnet/model.py:45-104): dx[ci][p] = sum_{t,co} dz[p - o(t)][co] w[co][ci][t].
+ * dmc_ctxends_first_wgrad (code/dmcnet/model.py:45-104): dw[co][ci][t] = sum_p dz[p][co] x[ci][p + o(t)]; every element of dw
+ *   is written (a tap no pixel reaches: 0).
+ * dmc_ctxends_heads_fwd (code/dmcnet/model.py:45-104): z_k[c][p] = sum_{t,ci} t[p + o(t)][ci] w_k[c][t][ci] for the flow head
+ *   and, when w_att and z_att are given (together or not at all), the attention head, in one launch that reads t once: the
+ *   sums of dmc_ctx_heads_eval, bit for bit.
+ * dmc_ctxends_heads_dgrad (code/dmcnet/model.py:45-104): dt[p][ci] = sum over the heads of sum_{t,c} dz_k[c][p - o(t)]
+ *   w_k[c][t][ci], both heads in one launch.  w_att NULL: a network with one head (dz_att must be NULL too).  With w_att, a NULL
+ *   dz_flow or dz_att means that head got no gradient (at least one is given).
+ * dmc_ctxends_heads_wgrad (code/dmcnet/model.py:45-104): dw_k[c][t][ci] = sum_q t[q][ci] dz_k[c][q - o(t)] for every head whose
+ *   (dz, dw) pair is given (a pair is present or absent together; at least one pair); a head without a pair is not touched.
+ * dmc_ctxends_bn_fwd (code/dmcnet/model.py:45-104): on the planes z [N][2][H][W] with statistics over M = N H W per channel:
+ *   stats = (mean[2], invstd[2]), sums and statistics in fp64 exactly as dmc_bnlrelu_fwd; y = t > 0 ? t : slope * t with
+ *   t = fmaf((z - mean) * invstd, gamma, beta), and y = max(y, 0) when relu != 0 (the attention head).  running_mean /
+ *   running_var as dmc_bnlrelu_fwd.
+ * dmc_ctxends_bn_bwd (code/dmcnet/model.py:45-104): from z, dy and the forward's stats (y is not read):
+ *   g = dy * (t > 0 ? 1 : slope), or dy * (t > 0 ? 1 : 0) when relu != 0 (t == 0 takes the lower branch); dbeta = sum g,
+ *   dgamma = sum g xhat (fp64 sums), dz = gamma invstd (g - dbeta / M - xhat dgamma / M).
+ * Deterministic, no atomics: bit-identical from run to run; the forward / data gradients of a frame are independent of its batch.
+ * Inputs are read only.  H * W may be odd (planes need no 16-byte alignment).
+ * DMC_E_INVALID before any launch (nothing written): a NULL required pointer, a half-given attention group or (dz, dw) pair,
+ * exactly one running pointer, a shape outside dmc_ctxends_supported() (N * H * W < 2 for the BatchNorm), eps <= 0, slope
+ * outside (0, 1), momentum outside [0, 1]. */
+int dmc_ctxends_supported(int N, int H, int W);
+size_t dmc_ctxends_wgrad_workspace_bytes(int N, int H, int W, int planes);
+size_t dmc_ctxends_bn_scratch_bytes(int N, int H, int W);
+int dmc_ctxends_first_fwd(const float* x, const float* w, float* z, int N, int H, int W, dmc_stream_t stream);
+int dmc_ctxends_first_dgrad(const float* dz, const float* w, float* dx, int N, int H, int W, dmc_stream_t stream);
+int dmc_ctxends_first_wgrad(const float* x, const float* dz, float* dw, void* workspace, int N, int H, int W, dmc_stream_t stream);
+int dmc_ctxends_heads_fwd(const float* t, const float* w_flow, const float* w_att, float* z_flow, float* z_att, int N, int H, int W,
+                          dmc_stream_t stream);
+int dmc_ctxends_heads_dgrad(const float* dz_flow, const float* dz_att, const float* w_flow, const float* w_att, float* dt, int N,
+                            int H, int W, dmc_stream_t stream);
+int dmc_ctxends_heads_wgrad(const float* t, const float* dz_flow, const float* dz_att, float* dw_flow, float* dw_att,
+                            void* workspace, int N, int H, int W, dmc_stream_t stream);
+int dmc_ctxends_bn_fwd(const float* z, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                       float* stats, void* scratch, int N, int H, int W, float slope, float eps, float momentum, int relu,
+                       dmc_stream_t stream);
+int dmc_ctxends_bn_bwd(const float* z, const float* dy, const float* gamma, const float* beta, const float* stats, void* scratch,
+                       float* dz, float* dgamma, float* dbeta, int N, int H, int W, float slope, int relu, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

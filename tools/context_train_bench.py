@@ -15,8 +15,11 @@ share of the bf16x3 bound (2,500 / 6 = 416.7 TFLOP/s), the ratio stock / ours, t
 library's source hashes; ``--table`` also prints the rows as a Markdown table.
 ``--bn`` prints the BatchNorm + LeakyReLU table instead (bn_table below: ops.bn_leaky per unit width, and the whole step on the
 three routes stock / CTX_TRAIN / CTX_TRAIN + CTX_TRAIN_BN; recorded in profiles/context_train_bn_bench.json).
+``--ends`` prints the table of the two ends instead (ends_table below: the first unit's and the heads' convolution passes and the
+heads' BatchNorm through the C ABI, and the whole step on four routes, the last with CTX_TRAIN_ENDS as well; recorded in
+profiles/context_train_ends_bench.json with the sources' sha256).
 
-    python tools/context_train_bench.py [--bn] [--frames 24] [--size 224] [--warmup 2] [--iters 5] [--pairs 3] [--table] [--out FILE]"""
+    python tools/context_train_bench.py [--bn | --ends] [--frames 24] [--size 224] [--warmup 2] [--iters 5] [--pairs 3] [--table] [--out FILE]"""
 import argparse
 import hashlib
 import json
@@ -189,6 +192,192 @@ def bn_table(args):
             f.write(line + "\n")
 
 
+def ends_table(args):
+    """--ends: the two ends (csrc/ctx_ends.hip, what DMC_CTX_TRAIN_ENDS=1 adds) against the stock modules.
+      * per pass: ours through the C ABI against the stock convolution(s) / BatchNorm2d(2) + LeakyReLU on channels_last tensors (the
+        gradients as torch.autograd.grad of their graph; ContextNetworkAtt's stock heads count both heads and the gradient add),
+        bytes from the shapes as TB/s;
+      * the whole training step of both networks on four routes in one process: stock, CTX_TRAIN, + CTX_TRAIN_BN,
+        + CTX_TRAIN_BN + CTX_TRAIN_ENDS; every pair's times are kept, the order rotates from pair to pair."""
+    import torch
+    import torch.nn.functional as F
+    if not torch.cuda.is_available():
+        raise SystemExit("context_train_bench: needs a GPU (no CPU timing)")
+    from dmcnet_amd import _lib, model, ops
+    from oracle import dmc_oracle as O
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    CL = torch.channels_last
+    P = _lib.ptr
+    n, h, w = args.frames, args.size, args.size
+    M = n * h * w
+    g = torch.Generator(device=dev).manual_seed(24 + n)
+    s = ops._stream()
+    slope, eps, mom = 0.1, 1e-5, 0.1
+    passes, steps = [], []
+
+    def rel(a, b):
+        return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
+
+    def row(name, floats_per_pixel, ours, stock, cmp):
+        best, last = alternate(ours, stock, args.warmup, args.iters, args.pairs)
+        nbytes = 4.0 * M * floats_per_pixel
+        tbs = nbytes / best["ours"] / 1e9
+        passes.append({"pass": name, "ours_ms": round(best["ours"], 4), "stock_ms": round(best["stock"], 4),
+                       "stock_over_ours": round(best["stock"] / best["ours"], 3), "mbytes": round(nbytes / 1e6, 1), "ours_tbs": round(tbs, 3),
+                       "ours_share_of_achievable": round(tbs / HBM_ACHIEVABLE_TBS, 3), "rel_err_ours_vs_stock": cmp(last["ours"], last["stock"])})
+        print("# %s: ours %.3f ms (%.2f TB/s), stock %.3f ms" % (name, best["ours"], tbs, best["stock"]), file=sys.stderr, flush=True)
+
+    net0 = O.seeded_state_fill(model.ContextNetworkAtt(5, True, 0), seed=26).to(dev).train()
+    # ---- the first unit's convolution
+    w1 = net0.conv_context[0][0].weight.detach().contiguous()
+    x = torch.randn((n, 5, h, w), generator=g, device=dev)
+    dz = torch.randn((n, 32, h, w), generator=g, device=dev).contiguous(memory_format=CL)
+    z = torch.empty((n, 32, h, w), device=dev, memory_format=CL)
+    dx, dw1 = torch.empty_like(x), torch.empty_like(w1)
+    work = torch.empty(lib.dmc_ctxends_wgrad_workspace_bytes(n, h, w, 5), dtype=torch.uint8, device=dev)
+    xs, ws = x.contiguous(memory_format=CL).requires_grad_(True), w1.contiguous(memory_format=CL).requires_grad_(True)
+    zs = F.conv2d(xs, ws, None, 1, 1, 1)
+
+    def first_fwd():
+        _lib.check(lib.dmc_ctxends_first_fwd(P(x), P(w1), P(z), n, h, w, s), "dmc_ctxends_first_fwd")
+        return z
+
+    def first_dgrad():
+        _lib.check(lib.dmc_ctxends_first_dgrad(P(dz), P(w1), P(dx), n, h, w, s), "dmc_ctxends_first_dgrad")
+        return dx
+
+    def first_wgrad():
+        _lib.check(lib.dmc_ctxends_first_wgrad(P(x), P(dz), P(dw1), P(work), n, h, w, s), "dmc_ctxends_first_wgrad")
+        return dw1
+
+    with torch.no_grad():
+        row("first 5->32 forward", 37, first_fwd, lambda: F.conv2d(xs, ws, None, 1, 1, 1), rel)
+    row("first 5->32 data gradient", 37, first_dgrad, lambda: torch.autograd.grad(zs, xs, dz, retain_graph=True)[0], rel)
+    row("first 5->32 weight gradient", 37, first_wgrad, lambda: torch.autograd.grad(zs, ws, dz, retain_graph=True)[0], rel)
+    del x, dz, z, dx, xs, zs, work
+    torch.cuda.empty_cache()
+    # ---- the heads' convolutions (ContextNetworkAtt: both heads)
+    wh = [net0.predict_flow[0].weight.detach().contiguous(memory_format=CL), net0.predict_att[0][0].weight.detach().contiguous(memory_format=CL)]
+    t = torch.randn((n, 32, h, w), generator=g, device=dev).contiguous(memory_format=CL)
+    dzh = [torch.randn((n, 2, h, w), generator=g, device=dev) for _ in range(2)]
+    dzh_cl = [d.contiguous(memory_format=CL) for d in dzh]
+    zh = [torch.empty((n, 2, h, w), device=dev) for _ in range(2)]
+    dt = torch.empty_like(t)
+    dwh = [torch.empty_like(wt) for wt in wh]
+    work = torch.empty(lib.dmc_ctxends_wgrad_workspace_bytes(n, h, w, 4), dtype=torch.uint8, device=dev)
+    ts, whs = t.clone().requires_grad_(True), [wt.clone().requires_grad_(True) for wt in wh]
+    zhs = [F.conv2d(ts, wt, None, 1, 1, 1) for wt in whs]
+
+    def heads_fwd():
+        _lib.check(lib.dmc_ctxends_heads_fwd(P(t), P(wh[0]), P(wh[1]), P(zh[0]), P(zh[1]), n, h, w, s), "dmc_ctxends_heads_fwd")
+        return torch.cat(zh)
+
+    def heads_dgrad():
+        _lib.check(lib.dmc_ctxends_heads_dgrad(P(dzh[0]), P(dzh[1]), P(wh[0]), P(wh[1]), P(dt), n, h, w, s), "dmc_ctxends_heads_dgrad")
+        return dt
+
+    def heads_wgrad():
+        _lib.check(lib.dmc_ctxends_heads_wgrad(P(t), P(dzh[0]), P(dzh[1]), P(dwh[0]), P(dwh[1]), P(work), n, h, w, s), "dmc_ctxends_heads_wgrad")
+        return torch.cat(dwh)
+
+    with torch.no_grad():
+        row("heads 32->2 x2 forward", 36, heads_fwd, lambda: torch.cat([F.conv2d(t, wt, None, 1, 1, 1) for wt in wh]), rel)
+    row("heads 32->2 x2 data gradient (+ add)", 36, heads_dgrad, lambda: torch.autograd.grad(zhs, ts, dzh_cl, retain_graph=True)[0], rel)
+    row("heads 32->2 x2 weight gradient", 36, heads_wgrad, lambda: torch.cat(torch.autograd.grad(zhs, whs, dzh_cl, retain_graph=True)), rel)
+    del t, dt, ts, zhs, work
+    torch.cuda.empty_cache()
+    # ---- one head's BatchNorm2d(2) + LeakyReLU
+    bn, act = net0.predict_flow[1], torch.nn.LeakyReLU(slope, inplace=True)
+    zb, dyb = dzh[0], dzh[1]
+    zb_cl, dyb_cl = dzh_cl[0], dzh_cl[1]
+    gamma, beta = bn.weight.detach(), bn.bias.detach()
+    rm, rv = bn.running_mean.clone(), bn.running_var.clone()
+    yb, dzb = torch.empty_like(zb), torch.empty_like(zb)
+    stats, dgamma, dbeta = torch.empty(4, device=dev), torch.empty(2, device=dev), torch.empty(2, device=dev)
+    scratch = torch.empty(lib.dmc_ctxends_bn_scratch_bytes(n, h, w), dtype=torch.uint8, device=dev)
+
+    def bn_fwd():
+        _lib.check(lib.dmc_ctxends_bn_fwd(P(zb), P(gamma), P(beta), P(rm), P(rv), P(yb), P(stats), P(scratch), n, h, w, slope, eps, mom, 0, s),
+                   "dmc_ctxends_bn_fwd")
+        return yb
+
+    def bn_bwd():
+        _lib.check(lib.dmc_ctxends_bn_bwd(P(zb), P(dyb), P(gamma), P(beta), P(stats), P(scratch), P(dzb), P(dgamma), P(dbeta), n, h, w, slope, 0, s),
+                   "dmc_ctxends_bn_bwd")
+        return dzb
+
+    with torch.no_grad():
+        row("head BatchNorm(2) + LeakyReLU forward", 6, bn_fwd, lambda: act(bn(zb_cl)), rel)
+    zbs = zb_cl.clone().requires_grad_(True)
+    ybs = act(bn(zbs))
+    row("head BatchNorm(2) + LeakyReLU backward", 10, bn_bwd, lambda: torch.autograd.grad(ybs, (zbs, bn.weight, bn.bias), dyb_cl, retain_graph=True)[0], rel)
+    del zbs, ybs, dzh, dzh_cl
+    torch.cuda.empty_cache()
+
+    routes = (("stock", False, False, False), ("ctx_train", True, False, False), ("ctx_train_bn", True, True, False),
+              ("ctx_train_bn_ends", True, True, True))
+    for att in [int(a) for a in args.nets.split(",") if a != ""]:
+        cls = model.ContextNetworkAtt if att else model.ContextNetwork
+        net = O.seeded_state_fill(cls(5, True, 0), seed=26).to(dev).train()
+        x = torch.randn((n, 5, h, w), generator=g, device=dev)
+        r = torch.randn((n, 2, h, w), generator=g, device=dev)
+
+        def step(train, bn_on, ends_on):
+            model.CTX_TRAIN, model.CTX_TRAIN_BN, model.CTX_TRAIN_ENDS = train, bn_on, ends_on
+            try:
+                for p in net.parameters():
+                    p.grad = None
+                xi = x.clone().requires_grad_(True)
+                out = net(xi)
+                outs = out if isinstance(out, tuple) else (out,)
+                sum((t * r).sum() for t in outs).backward()
+            finally:
+                model.CTX_TRAIN, model.CTX_TRAIN_BN, model.CTX_TRAIN_ENDS = False, False, False
+            return torch.cat([xi.grad.reshape(-1)] + [p.grad.reshape(-1) for p in net.parameters()])
+
+        for _ in range(args.warmup):
+            for _, a, b, c in routes:
+                step(a, b, c)
+        per_pair, last = [], {}
+        for p in range(args.pairs):
+            order = routes[p % 4:] + routes[:p % 4]
+            ms = {}
+            for name, a, b, c in order:
+                ms[name], last[name] = timed(lambda: step(a, b, c), args.iters)
+            per_pair.append({k: round(v, 3) for k, v in ms.items()})
+        res = {"network": cls.__name__, "frames": n, "pairs": per_pair,
+               "best_ms": {name: min(p[name] for p in per_pair) for name, _, _, _ in routes},
+               "ends_faster_than_ctx_train_bn_in_every_pair": all(p["ctx_train_bn_ends"] < p["ctx_train_bn"] for p in per_pair),
+               "rel_err_ends_vs_stock": rel(last["ctx_train_bn_ends"], last["stock"]), "rel_err_bn_vs_stock": rel(last["ctx_train_bn"], last["stock"])}
+        steps.append(res)
+        print("# %s: %s" % (cls.__name__, per_pair), file=sys.stderr, flush=True)
+        del x, r, last, net
+        torch.cuda.empty_cache()
+
+    res = {"tool": "context_train_bench --ends", "device": torch.cuda.get_device_name(0), "size": args.size, "frames": n,
+           "hbm_achievable_tbs": HBM_ACHIEVABLE_TBS, "warmup": args.warmup, "iters": args.iters, "pairs": args.pairs,
+           "sources_sha256": sources_hash(), "sources": __import__("dmcnet_amd.build", fromlist=["source_hashes"]).source_hashes(),
+           "passes": passes, "steps": steps}
+    line = json.dumps(res, sort_keys=True)
+    print(line, flush=True)
+    if args.table:
+        print("| pass | MB | ours ms | stock ms | stock / ours | ours TB/s | of %.1f | ours vs stock |" % HBM_ACHIEVABLE_TBS)
+        print("|---|---|---|---|---|---|---|---|")
+        for u in passes:
+            print("| %s | %.0f | %.3f | %.3f | %.2f | %.2f | %.0f %% | %.1e |" % (
+                u["pass"], u["mbytes"], u["ours_ms"], u["stock_ms"], u["stock_over_ours"], u["ours_tbs"], 100 * u["ours_share_of_achievable"],
+                u["rel_err_ours_vs_stock"]))
+        print("| network | pair | stock ms | CTX_TRAIN ms | + BN ms | + BN + ENDS ms |")
+        print("|---|---|---|---|---|---|")
+        for st in steps:
+            for i, p in enumerate(st["pairs"]):
+                print("| %s | %d | %.2f | %.2f | %.2f | %.2f |" % (st["network"], i + 1, p["stock"], p["ctx_train"], p["ctx_train_bn"], p["ctx_train_bn_ends"]))
+    out = args.out or os.path.join(ROOT, "profiles", "context_train_ends_bench.json")
+    with open(out, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=24)
@@ -200,9 +389,13 @@ def main():
     ap.add_argument("--table", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--bn", action="store_true", help="the BatchNorm + LeakyReLU table (ops.bn_leaky, CTX_TRAIN_BN) instead of the convolutions'")
+    ap.add_argument("--ends", action="store_true", help="the first unit's and the heads' table (csrc/ctx_ends.hip, CTX_TRAIN_ENDS); writes "
+                                                        "profiles/context_train_ends_bench.json unless --out says otherwise")
     args = ap.parse_args()
     if args.bn:
         return bn_table(args)
+    if args.ends:
+        return ends_table(args)
 
     import torch
     import torch.nn.functional as F
