@@ -194,6 +194,12 @@ SIGNATURES = {
     "dmc_ctxends_heads_wgrad": (_I, [_P] * 6 + [_I] * 3 + [_P]),
     "dmc_ctxends_bn_fwd": (_I, [_P] * 8 + [_I] * 3 + [_F, _F, _F, _I, _P]),
     "dmc_ctxends_bn_bwd": (_I, [_P] * 9 + [_I] * 3 + [_F, _I, _P]),
+    "dmc_dense_supported": (_I, [_I] * 6),
+    "dmc_dense_wpack_bytes": (_Z, [_I, _I]),
+    "dmc_dense_pack_weights": (_I, [_P, _P, _I, _I, _P]),
+    "dmc_dense_ingest": (_I, [_P, _P] + [_I] * 4 + [_P]),
+    "dmc_dense_layer_eval": (_I, [_P] * 3 + [_I] * 6 + [_P]),
+    "dmc_dense_head_eval": (_I, [_P] * 4 + [_I] * 5 + [_P]),
 }
 
 _lib = None

@@ -7,7 +7,8 @@ code/dmcnet_GAN/model.py:442-585 (paths relative to the reference root).  What d
 where the arithmetic runs: the DenseNetTiny generator (+ cat + delta add), the ResNet's
 convolutions / BatchNorms / stem (``resnet.py`` -> ``ops.conv_bn_act``, ``ops.stem_conv``, ...) and
 the Discriminator3 blocks (``ops.disc_block``) are hand-written HIP kernels behind the C ABI, and so
-are ContextNetwork / ContextNetworkAtt in eval mode (``ops.context_eval``); only the API-only
+are ContextNetwork / ContextNetworkAtt in eval mode (``ops.context_eval``) and, with autograd off, EstimatorDenseNet (and, with
+``DMC_DENSE_EVAL=1``, EstimatorDenseNetSmall) without their concatenations (``ops.dense_eval``, csrc/dense_eval.hip); only the API-only
 estimator / discriminator variants, by default the training of the ContextNetworks, and the two
 ``nn.Linear`` heads stay on PyTorch-ROCm ops.  With ``DMC_CTX_TRAIN=1`` (``CTX_TRAIN``, off by default)
 the dilated convolutions of the ContextNetworks' five middle units -- forward, data gradient and weight
@@ -32,6 +33,15 @@ from . import ops, resnet, transforms
 #: per dilated conv + BatchNorm + LeakyReLU unit) whenever ops.context_eval_supported accepts the network and the input.
 #: DMC_CTX_EVAL=0 (read once, here): always the stock modules -- A/B measurements, and a safety valve.
 CTX_EVAL = _os.environ.get("DMC_CTX_EVAL", "1") != "0"
+#: EstimatorDenseNet / EstimatorDenseNetSmall under no_grad run on the kernels of csrc/dense_eval.hip (ops.dense_eval: one feature
+#: buffer that every layer reads a prefix of and appends to, no concatenation) whenever ops.dense_eval_supported accepts the network
+#: and the input.  DMC_DENSE_EVAL=0 (read once, here): always the stock modules, bit for bit.  Training and any call with autograd
+#: enabled keep the stock modules whatever the flag says.
+DENSE_EVAL = _os.environ.get("DMC_DENSE_EVAL", "1") != "0"
+#: DMC_DENSE_EVAL=1 set explicitly (read once, here): also the classes whose route measured SLOWER than the stock modules on the
+#: evaluator's batch (DENSE_EVAL_BY_DEFAULT = False: EstimatorDenseNetSmall, 0.82x at 25 frames of 224 x 224).  Unset, such
+#: a class takes the route only where the stock route cannot be trusted: when its widest concatenation reaches 4 GiB.
+DENSE_EVAL_ALL = _os.environ.get("DMC_DENSE_EVAL", "") == "1"
 #: DMC_CTX_TRAIN=1 (read once, here; default 0): with autograd enabled, the convolutions of the five middle units of ContextNetwork /
 #: ContextNetworkAtt run on the kernels of csrc/dconv.hip (ops.context_train: ops.dilated_conv per unit, then the unit's own
 #: BatchNorm2d and LeakyReLU; the first unit and the heads stay stock) whenever ops.context_train_supported accepts the network
@@ -71,7 +81,16 @@ class DenseEstimatorBase(nn.Module):
         self.predict_flow = nn.Conv2d(total, 2, kernel_size=3, stride=1, padding=1, bias=True)
         self.depth = len(widths)
 
+    #: False on a class whose eval route measured slower than the stock modules (see DENSE_EVAL_ALL)
+    DENSE_EVAL_BY_DEFAULT = True
+
+    def _stock_passes_4gib(self, x):
+        """True if the widest tensor of the stock forward on ``x`` -- predict_flow's input, the last concatenation -- has 4 GiB or more."""
+        return torch.is_tensor(x) and x.dim() == 4 and x.shape[0] * x.shape[2] * x.shape[3] * self.predict_flow.in_channels * 4 >= 1 << 32
+
     def forward(self, x):
+        if DENSE_EVAL and (DENSE_EVAL_ALL or self.DENSE_EVAL_BY_DEFAULT or self._stock_passes_4gib(x)) and ops.dense_eval_supported(self, x):
+            return ops.dense_eval(self, x)
         for i in range(self.depth):
             x = torch.cat((getattr(self, "conv_%d" % i)(x), x), 1)
         return self.predict_flow(x)
@@ -83,6 +102,8 @@ class EstimatorDenseNet(DenseEstimatorBase):
 
 
 class EstimatorDenseNetSmall(DenseEstimatorBase):
+    DENSE_EVAL_BY_DEFAULT = False       # 32-wide layers: the route runs at 0.62-0.82x of the stock modules
+
     def __init__(self, ch_in=5):
         super().__init__(_DENSE["DenseNetSmall"], ch_in)
 

@@ -2729,6 +2729,164 @@ def context_eval(net, x):
     return out_flow
 
 
+# ---- EstimatorDenseNet / EstimatorDenseNetSmall in eval mode: one feature buffer instead of the concatenations (csrc/dense_eval.hip) ----
+
+#: bytes one feature buffer may take (dense_eval_chunks' default): the evaluator's 25-frame batch of 224 x 224 is one frame range for
+#: both networks (2.33 GB at 464 channels)
+DENSE_EVAL_BUDGET = 4 << 30
+_DENSE_MAX_INDEX = 1 << 31     # one launch indexes frames * H * W * CT below this
+_DENSE_SLOPE = 0.1
+_DENSE_SLOT0 = 16              # the input's slot: ch_in live channels, zeros up to 16
+
+
+def dense_eval_layout(widths, ch_in=5):
+    """The feature buffer of a dense stack with layer widths ``widths`` over ``ch_in`` input channels, as a dict:
+      "offsets"  first buffer channel of slot 0 (the input, 16 wide) and of slot k + 1 (the output of conv_k, round_up(width, 32) wide);
+      "ct"       channels per pixel of the buffer;
+      "layers"   per conv_k: (K, R, index) -- it reads buffer channels [0, K) and writes [K, K + R); ``index`` (int64 [K]) maps a
+                 buffer channel to the input channel of the reference's conv_k, whose input is cat(y_{k-1}, ..., y_0, x), or -1 for a pad;
+      "head"     (K, 2, index) of predict_flow the same way, K = ct.
+    A pure function of its arguments."""
+    widths = [int(v) for v in widths]
+    ch_in = int(ch_in)
+    if not widths or min(widths) <= 0 or not 0 < ch_in <= _DENSE_SLOT0:
+        raise ValueError("dense_eval_layout: widths must be positive and 0 < ch_in <= %d" % _DENSE_SLOT0)
+    offsets = [0, _DENSE_SLOT0]
+    for v in widths:
+        offsets.append(offsets[-1] + (v + 31) // 32 * 32)
+    live = [ch_in] + widths                                        # live channels per slot
+
+    def index(k):                                                  # the input of conv_k (k == len(widths): predict_flow)
+        idx = torch.full((offsets[k + 1],), -1, dtype=torch.int64)
+        ref = sum(widths[:k])                                      # x comes last in the reference's order ...
+        idx[0:ch_in] = torch.arange(ref, ref + ch_in)
+        for j in range(k):                                         # ... behind y_0, which is behind y_1, ...
+            ref -= widths[j]
+            idx[offsets[j + 1]:offsets[j + 1] + live[j + 1]] = torch.arange(ref, ref + widths[j])
+        return idx
+
+    layers = [(offsets[k + 1], offsets[k + 2] - offsets[k + 1], index(k)) for k in range(len(widths))]
+    return {"offsets": offsets[:-1], "ct": offsets[-1], "layers": layers, "head": (offsets[-1], 2, index(len(widths)))}
+
+
+def dense_eval_chunks(n, h, w, ct, budget_bytes=None):
+    """Frame ranges [(a, b), ...] of the feature buffers that evaluate ``n`` frames of ``h`` x ``w`` with ``ct`` buffer channels: they
+    tile [0, n) in order, each keeps frames * h * w * ct below 2^31 (what dmc_dense_supported accepts) and its fp32 buffer within
+    ``budget_bytes`` (default DENSE_EVAL_BUDGET).  ValueError when a single frame does not fit.  A pure function of its arguments."""
+    n, h, w, ct = int(n), int(h), int(w), int(ct)
+    budget = DENSE_EVAL_BUDGET if budget_bytes is None else int(budget_bytes)
+    if n <= 0 or h <= 0 or w <= 0 or ct <= 0:
+        raise ValueError("dense_eval_chunks: sizes must be positive")
+    per = min((_DENSE_MAX_INDEX - 1) // (h * w * ct), budget // (h * w * ct * 4))
+    if per <= 0:
+        raise ValueError("dense_eval_chunks: one %d x %d frame of %d channels is more than a launch can index or the budget holds" % (h, w, ct))
+    return [(a, min(a + per, n)) for a in range(0, n, per)]
+
+
+def _dense_conv_ok(conv, cin, cout=None, on_device=True):
+    if not isinstance(conv, torch.nn.Conv2d) or conv.bias is None or conv.groups != 1 or conv.padding_mode != "zeros":
+        return False
+    if tuple(conv.kernel_size) != (3, 3) or tuple(conv.stride) != (1, 1) or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1):
+        return False
+    if conv.in_channels != cin or (cout is not None and conv.out_channels != cout):
+        return False
+    return all((p.is_cuda or not on_device) and p.dtype == torch.float32 for p in (conv.weight, conv.bias))
+
+
+def _dense_plan(net, on_device=True):
+    """([conv_0, ...], predict_flow) of a dense estimator (model.DenseEstimatorBase) whose every unit the eval kernels serve, or None.
+    ``on_device=False`` leaves out the one test that needs a GPU, that the parameters are CUDA tensors (the structural part alone)."""
+    depth = getattr(net, "depth", None)
+    if not isinstance(depth, int) or depth <= 0:
+        return None
+    convs, c = [], 5
+    for i in range(depth):
+        unit = getattr(net, "conv_%d" % i, None)
+        if not isinstance(unit, torch.nn.Sequential) or len(unit) != 2 or not isinstance(unit[1], torch.nn.LeakyReLU):
+            return None
+        if abs(unit[1].negative_slope - _DENSE_SLOPE) > 1e-12 or not _dense_conv_ok(unit[0], c, None, on_device) or unit[0].out_channels > 128:
+            return None
+        convs.append(unit[0])
+        c += unit[0].out_channels
+    head = getattr(net, "predict_flow", None)
+    if not _dense_conv_ok(head, c, 2, on_device):
+        return None
+    return convs, head
+
+
+def dense_eval_supported(net, x):
+    """True if ``net`` (model.EstimatorDenseNet / EstimatorDenseNetSmall: a DenseEstimatorBase with the stock forward) can be evaluated
+    on ``x`` by the kernels of csrc/dense_eval.hip: no autograd, a non-empty CUDA fp32 [N, 5, H, W] input, every unit a
+    Sequential(Conv2d 3x3 / stride 1 / padding 1 with bias, LeakyReLU(0.1)) of at most 128 channels whose inputs chain as the
+    concatenations do, predict_flow a Conv2d of the same geometry with 2 channels, CUDA fp32 parameters, a frame range that
+    fits (dense_eval_chunks) and every layer accepted by dmc_dense_supported."""
+    if torch.is_grad_enabled():
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 5 and x.numel() > 0):
+        return False
+    plan = _dense_plan(net)
+    if plan is None:
+        return False
+    lay = dense_eval_layout([c.out_channels for c in plan[0]])
+    n, _, h, w = x.shape
+    try:
+        a, b = dense_eval_chunks(n, h, w, lay["ct"])[0]
+    except ValueError:
+        return False
+    lib = _lib.load()
+    return all(lib.dmc_dense_supported(b - a, h, w, lay["ct"], k, r) for k, r, _ in lay["layers"] + [lay["head"]])
+
+
+def _dense_weight(conv, k, r, index):
+    """(weight OHWI [r][3][3][k], bias [r]) of ``conv`` in buffer order: input channel ``index[b]`` of the module at buffer channel b,
+    zeros in the pad columns, the pad rows and the pad bias entries."""
+    w = conv.weight.detach().permute(0, 2, 3, 1)
+    index = index.to(w.device)
+    live = (index >= 0).nonzero().reshape(-1)
+    wp = torch.zeros((r, 3, 3, k), dtype=torch.float32, device=w.device)
+    wp[:conv.out_channels].index_copy_(3, live, w.index_select(3, index[live]))
+    bp = torch.zeros((r,), dtype=torch.float32, device=w.device)
+    bp[:conv.out_channels] = conv.bias.detach()
+    return wp, bp
+
+
+def dense_eval(net, x):
+    """``net(x)`` of an EstimatorDenseNet / EstimatorDenseNetSmall (-> gen_flow [N, 2, H, W]) in eval mode on the kernels of
+    csrc/dense_eval.hip: per frame range (dense_eval_chunks) one NHWC fp32 feature buffer, the ingest, one launch per layer that
+    reads a prefix of the buffer and appends its slot, and the head -- no concatenation.  The weights are permuted into buffer order,
+    padded and split into bf16 slices once per call.  Requires dense_eval_supported(net, x)."""
+    lib = _lib.load()
+    if not dense_eval_supported(net, x):
+        raise _lib.DmcHipError("dense_eval: the network or the input is not served by the eval kernels (dense_eval_supported)")
+    convs, head = _dense_plan(net)
+    lay = dense_eval_layout([c.out_channels for c in convs])
+    ct = lay["ct"]
+    x = x.contiguous()
+    n, _, h, w = x.shape
+    dev = x.device
+    s = _stream()
+    with _span("dense_eval"):
+        layers = []
+        for conv, (k, r, index) in zip(convs, lay["layers"]):
+            wp, bp = _dense_weight(conv, k, r, index)
+            pack = torch.empty(lib.dmc_dense_wpack_bytes(k, r), dtype=torch.uint8, device=dev)
+            _lib.check(lib.dmc_dense_pack_weights(_lib.ptr(wp), _lib.ptr(pack), k, r, s), "dmc_dense_pack_weights")
+            layers.append((pack, bp, k, r))
+        hk, _, hindex = lay["head"]
+        hw_, hb = _dense_weight(head, hk, 2, hindex)
+        out = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        for a, b in dense_eval_chunks(n, h, w, ct):
+            f = b - a
+            feat = torch.empty((f, h, w, ct), dtype=torch.float32, device=dev)
+            _lib.check(lib.dmc_dense_ingest(_lib.ptr(x[a:b]), _lib.ptr(feat), f, h, w, ct, s), "dmc_dense_ingest")
+            for pack, bp, k, r in layers:
+                _lib.check(lib.dmc_dense_layer_eval(_lib.ptr(feat), _lib.ptr(pack), _lib.ptr(bp), f, h, w, ct, k, r, s), "dmc_dense_layer_eval")
+            _lib.check(lib.dmc_dense_head_eval(_lib.ptr(feat), _lib.ptr(hw_), _lib.ptr(hb), _lib.ptr(out[a:b]), f, h, w, ct, hk, s),
+                       "dmc_dense_head_eval")
+            del feat
+    return out
+
+
 # ---- ContextNetwork / ContextNetworkAtt in training: the dilated convolutions of the middle units (csrc/dconv.hip) ----
 
 def _dconv_geom_ok(x, cin, cout, dilation):

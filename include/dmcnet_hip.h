@@ -971,6 +971,35 @@ int dmc_ctxends_bn_fwd(const float* z, const float* gamma, const float* beta, fl
 int dmc_ctxends_bn_bwd(const float* z, const float* dy, const float* gamma, const float* beta, const float* stats, void* scratch,
                        float* dz, float* dgamma, float* dbeta, int N, int H, int W, float slope, int relu, dmc_stream_t stream);
 
+/* ---- EstimatorDenseNet / EstimatorDenseNetSmall in eval mode (csrc/dense_eval.hip) ----
+ * Replaces: the dense stack of code/dmcnet/model.py:122-170 as the evaluator runs it under model.eval() + no_grad,
+ *           x = cat(LeakyReLU_0.1(conv_i(x)), x) five times and predict_flow, every convolution 3x3 / stride 1 / padding 1 with bias,
+ *           without materialising a concatenation.
+ * The feature buffer: feat NHWC fp32 [N][H][W][CT], channels in slots in production order: [0, 16) = the 5 input channels and 11
+ *   zeros, then the output of each layer padded with zeros to a multiple of 32 channels.  A layer reads the prefix [0, K) of every
+ *   pixel and writes [K, K + R) of the same buffer; the caller permutes each weight's input channels into buffer order, with
+ *   zero rows / columns / bias entries for the pad channels (ops.dense_eval_layout describes the order).
+ * dmc_dense_supported: 1 when N, H, W, CT > 0, CT % 4 == 0, K >= 16, K % 16 == 0, N * H * W * CT < 2^31 (what one launch indexes;
+ *   the caller splits larger batches into frame ranges) and either R in {32, 64, 96, 128} with K + R <= CT (a layer) or R == 2
+ *   with K <= CT, K <= 512 (the head); else 0.
+ * dmc_dense_wpack_bytes: K * R * 9 * 3 * 2, the bytes of a layer's weight pack; 0 for an unsupported (K, R).
+ * dmc_dense_pack_weights: w OHWI [R][3][3][K] fp32 (padded, buffer order) -> wpack: three bf16 slices, [tap][K / 16][slice][R][16].
+ * dmc_dense_ingest: x NCHW [N][5][H][W] -> feat[.][0, 16): the 5 values, then 11 zeros (+0.0).  CT >= 16; other channels untouched.
+ * dmc_dense_layer_eval: feat[.][K, K + R) = leaky_0.1(conv3x3(feat[.][0, K)) + bias[R]) in place; bf16x3 arithmetic on the matrix
+ *   cores.  Reads only channels < K, writes only channels in [K, K + R): every other byte of feat is left as it is.
+ * dmc_dense_head_eval: out NCHW [N][2][H][W] = conv3x3(feat[.][0, K)) + bias[2], w [2][3][3][K] in buffer order; fp32 FMAs in a
+ *   fixed order.
+ * Deterministic, no atomics, independent of the batch a frame is in; inputs are read only.
+ * DMC_E_INVALID before any launch (nothing written): a NULL pointer, a shape outside dmc_dense_supported(). */
+int dmc_dense_supported(int N, int H, int W, int CT, int K, int R);
+size_t dmc_dense_wpack_bytes(int K, int R);
+int dmc_dense_pack_weights(const float* w_ohwi_padded, void* wpack, int K, int R, dmc_stream_t stream);
+int dmc_dense_ingest(const float* x_nchw, float* feat, int N, int H, int W, int CT, dmc_stream_t stream);
+int dmc_dense_layer_eval(float* feat, const void* wpack, const float* bias, int N, int H, int W, int CT, int K, int R,
+                         dmc_stream_t stream);
+int dmc_dense_head_eval(const float* feat, const float* w, const float* bias, float* out_nchw, int N, int H, int W, int CT, int K,
+                        dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
