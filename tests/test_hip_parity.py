@@ -1015,6 +1015,8 @@ CONV_CASES = [  # (N, Cin, H, W, Cout, k, stride)
     (3, 64, 13, 9, 128, 3, 2),       # second-generation kernels on ragged sizes (odd rows / columns, partial tiles)
     (2, 64, 5, 3, 64, 3, 1),
     (1, 128, 6, 2, 64, 1, 1),
+    # every 16- / 32-channel row of this list gives a persistent wave of conv_small.hip at most ONE tile: the shapes at which its
+    # waves walk several (prefetch, double buffer, sums carried across visits) are in tests/test_csm_walk_gpu.py
     (3, 16, 9, 7, 16, 3, 1),         # the small-channel bf16x3 kernel (conv_small.hip) on ragged sizes: 16-pixel tiles that
     (1, 32, 5, 3, 32, 3, 1),         # straddle rows and images, a last tile with invalid pixels, a 1 x 1 image
     (2, 16, 1, 1, 16, 3, 1),
