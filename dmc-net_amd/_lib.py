@@ -200,6 +200,16 @@ SIGNATURES = {
     "dmc_dense_ingest": (_I, [_P, _P] + [_I] * 4 + [_P]),
     "dmc_dense_layer_eval": (_I, [_P] * 3 + [_I] * 6 + [_P]),
     "dmc_dense_head_eval": (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    "dmc_densetrain_supported": (_I, [_I] * 6),
+    "dmc_densetrain_mask_workspace_bytes": (_Z, [_I] * 4),
+    "dmc_densetrain_wgrad_workspace_bytes": (_Z, [_I] * 5),
+    "dmc_densetrain_head_workspace_bytes": (_Z, [_I] * 4),
+    "dmc_densetrain_head_dgrad": (_I, [_P] * 3 + [_I] * 4 + [_P]),
+    "dmc_densetrain_head_wgrad": (_I, [_P] * 5 + [_I] * 4 + [_P]),
+    "dmc_densetrain_mask": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "dmc_densetrain_layer_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "dmc_densetrain_layer_dgrad": (_I, [_P] * 2 + [_I] * 8 + [_P]),
+    "dmc_densetrain_export": (_I, [_P] * 2 + [_I] * 4 + [_P]),
 }
 
 _lib = None

@@ -8,7 +8,8 @@
 //   ingest  x NCHW [N][5][H][W] -> feat[m][0..16): one thread per pixel, four 16-byte stores
 //   layer   feat[m][K..K+R) = leaky(conv3x3(feat[.][0..K)) + bias): implicit GEMM over (tap, channel) on v_mfma_f32_32x32x16_bf16 in
 //           the bf16x3 arithmetic of ctx_common.h's gather_gemm -- the same loop with the contraction length K and the pixel
-//           stride CT as two numbers (gather_gemm has one, Cin, for both), dilation 1
+//           stride CT as two numbers (gather_gemm has one, Cin, for both), dilation 1: dense_common.h's dense_gemm, which the
+//           training route's data gradient shares (dense_train.hip)
 //   head    predict_flow (K -> 2, no activation), NCHW out: plain fp32 FMAs in the form of ctx_eval.hip's ctx_heads_kernel
 //   pack    ctxk::pack_kernel as it is, on the padded OHWI weight [R][3][3][K]: panels [9][K / 16][3][R][16] bf16
 //
@@ -27,128 +28,16 @@
 // No atomics; a pixel's sum is formed in one fixed order by one lane column of the matrix core whatever tile or batch the
 // pixel is in: results are bit-identical from run to run and independent of the batch.
 // All tensor offsets are 64-bit; dmc_dense_supported() bounds N H W CT below 2^31 so that the pixel index fits an int.
-#include "ctx_common.h"
-#include "mma_bf16.h"
+#include "dense_common.h"
 
 using namespace dmc;
 using namespace dmc::ctxk;
+using namespace dmc::densek;
 
 namespace {
 
 constexpr float SLOPE = 0.1f;
 constexpr int HEAD_KMAX = 512;
-
-struct DenseArgs {
-    float* feat;                    // [M][CT]; read below K, written in [K, K + 32 TN)
-    const unsigned short* wpack;    // [9][K / 16][3][R][16] bf16
-    const float* bias;              // [R]
-    int H, W, CT, K, M;             // M = N H W
-};
-
-// gather_gemm (ctx_common.h) with the pixel stride CT and the contraction length K apart, dilation 1.  Same ownership and the
-// same accumulator layout: on return the lane holds pixel m0 + 32 i + (lane & 31), channels 32 j + 8 gq + 4 (lane >> 5) + e in
-// acc[i][j][4 gq + e].  lds: GatherLds<TN>::BYTES bytes, 16-byte aligned.
-template <int TN, int TM>
-__device__ __forceinline__ int dense_gemm(const DenseArgs& a, char* lds, f32x16 (&acc)[TM][TN]) {
-    constexpr int COUT = GatherLds<TN>::COUT;
-    constexpr int CH = GatherLds<TN>::CH;
-    constexpr int NWR = (CH + 4095) / 4096;                // 16-byte pieces per thread
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, khalf = lane >> 5;
-    const int m0 = blockIdx.x * (128 * TM) + wave * (32 * TM);
-
-    // ---- this lane's pixels: offset of (n, y, x, 8 khalf) and the taps that fall inside the frame ----
-    long xbase[TM];
-    unsigned tmask[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + 32 * i + l31;
-        xbase[i] = 0; tmask[i] = 0;
-        if (m < a.M) {
-            const int hw = a.H * a.W;
-            const int rem = m % hw;
-            const int yy = rem / a.W, xx = rem - yy * a.W;
-            xbase[i] = (long)m * a.CT + 8 * khalf;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int iy = yy + t / 3 - 1, ix = xx + t % 3 - 1;
-                if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) tmask[i] |= 1u << t;
-            }
-        }
-    }
-
-    const int nkb = a.K >> 4;
-    const int nsteps = 9 * nkb;
-    int tap = 0, kb = 0;                                   // of the step being LOADED
-    f32x4 xlo[TM], xhi[TM];
-    u32x4 wr[NWR];
-    auto load_step = [&](int s) {
-        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-        const long toff = ((long)dy * a.W + dx) * a.CT + 16 * kb;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const bool ok = (tmask[i] >> tap) & 1;
-            const float* p = a.feat + (ok ? xbase[i] + toff : 0);          // (a masked lane reads channels 0..15 of pixel 0: below K)
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(p), hi = *reinterpret_cast<const f32x4*>(p + 4);
-            xlo[i] = ok ? lo : (f32x4){0.f, 0.f, 0.f, 0.f};
-            xhi[i] = ok ? hi : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-        const char* src = reinterpret_cast<const char*>(a.wpack) + (long)s * CH;
-#pragma unroll
-        for (int r = 0; r < NWR; ++r) {
-            const int o = (r * 256 + tid) * 16;
-            if (CH % 4096 == 0 || o < CH) wr[r] = *reinterpret_cast<const u32x4*>(src + o);
-        }
-        if (++kb == nkb) { kb = 0; ++tap; }
-    };
-    auto store_w = [&](int buf) {
-#pragma unroll
-        for (int r = 0; r < NWR; ++r) {
-            const int o = (r * 256 + tid) * 16;
-            if (CH % 4096 == 0 || o < CH) *reinterpret_cast<u32x4*>(lds + buf * CH + o) = wr[r];
-        }
-    };
-
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int foff = l31 * 32 + khalf * 16;                // this lane's fragment inside a [32][16] bf16 panel
-
-    load_step(0);
-    store_w(0);
-    __syncthreads();
-#pragma unroll 1
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
-        Split3 xs[TM];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) xs[i] = split8(xlo[i], xhi[i]);
-        if (s + 1 < nsteps) load_step(s + 1);              // in flight during the MFMAs below
-        const char* wb = lds + buf * CH + foff;
-        // the six slice products, grouped by weight slice: (0,2) (0,1) (0,0) | (1,1) (1,0) | (2,0)
-#pragma unroll
-        for (int wsl = 0; wsl < 3; ++wsl) {
-            u32x4 wf[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) wf[j] = *reinterpret_cast<const u32x4*>(wb + (wsl * COUT + 32 * j) * 32);
-#pragma unroll
-            for (int xsl = 2 - wsl; xsl >= 0; --xsl)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = mfma_bf16(wf[j], xs[i].s[xsl], acc[i][j]);
-        }
-        if (s + 1 < nsteps) store_w(buf ^ 1);              // nobody reads that buffer during this step
-        __syncthreads();
-    }
-    return m0;
-}
 
 template <int TN, int TM>
 __global__ __launch_bounds__(256) void dense_layer_kernel(DenseArgs a) {
@@ -285,6 +174,7 @@ int dmc_dense_layer_eval(float* feat, const void* wpack, const float* bias, int 
     DenseArgs a;
     a.feat = feat; a.wpack = reinterpret_cast<const unsigned short*>(wpack); a.bias = bias;
     a.H = H; a.W = W; a.CT = CT; a.K = K; a.M = N * H * W;
+    a.koff = 0; a.c0 = 0; a.cend = 0;
     constexpr int TM = 2;
     const dim3 grid((a.M + 128 * TM - 1) / (128 * TM));
     hipStream_t s = (hipStream_t)stream;

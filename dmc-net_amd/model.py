@@ -9,8 +9,9 @@ convolutions / BatchNorms / stem (``resnet.py`` -> ``ops.conv_bn_act``, ``ops.st
 the Discriminator3 blocks (``ops.disc_block``) are hand-written HIP kernels behind the C ABI, and so
 are ContextNetwork / ContextNetworkAtt in eval mode (``ops.context_eval``) and, with autograd off, EstimatorDenseNet (and, with
 ``DMC_DENSE_EVAL=1``, EstimatorDenseNetSmall) without their concatenations (``ops.dense_eval``, csrc/dense_eval.hip); only the API-only
-estimator / discriminator variants, by default the training of the ContextNetworks, and the two
-``nn.Linear`` heads stay on PyTorch-ROCm ops.  With ``DMC_CTX_TRAIN=1`` (``CTX_TRAIN``, off by default)
+estimator / discriminator variants, by default the training of the ContextNetworks and of the dense estimators, and the two
+``nn.Linear`` heads stay on PyTorch-ROCm ops.  With ``DMC_DENSE_TRAIN=1`` (``DENSE_TRAIN``, off by default) EstimatorDenseNet /
+EstimatorDenseNetSmall train on the feature buffer as well (``ops.dense_train``: forward csrc/dense_eval.hip, backward csrc/dense_train.hip).  With ``DMC_CTX_TRAIN=1`` (``CTX_TRAIN``, off by default)
 the dilated convolutions of the ContextNetworks' five middle units -- forward, data gradient and weight
 gradient, 99.4 % of the arithmetic -- run on csrc/dconv.hip (``ops.dilated_conv``) in training as well;
 their BatchNorms, LeakyReLUs, first unit and head(s) remain the stock modules.  ``DMC_CTX_TRAIN_BN=1``
@@ -42,6 +43,10 @@ DENSE_EVAL = _os.environ.get("DMC_DENSE_EVAL", "1") != "0"
 #: evaluator's batch (DENSE_EVAL_BY_DEFAULT = False: EstimatorDenseNetSmall, 0.82x at 25 frames of 224 x 224).  Unset, such
 #: a class takes the route only where the stock route cannot be trusted: when its widest concatenation reaches 4 GiB.
 DENSE_EVAL_ALL = _os.environ.get("DMC_DENSE_EVAL", "") == "1"
+#: DMC_DENSE_TRAIN=1 (read once, here; default 0): with autograd enabled, EstimatorDenseNet / EstimatorDenseNetSmall run as one autograd
+#: function on the feature buffer of the eval route -- forward csrc/dense_eval.hip, backward csrc/dense_train.hip (``ops.dense_train``)
+#: -- where ``ops.dense_train_supported`` accepts the network and the input; otherwise, and by default, the stock loop.
+DENSE_TRAIN = _os.environ.get("DMC_DENSE_TRAIN", "0") == "1"
 #: DMC_CTX_TRAIN=1 (read once, here; default 0): with autograd enabled, the convolutions of the five middle units of ContextNetwork /
 #: ContextNetworkAtt run on the kernels of csrc/dconv.hip (ops.context_train: ops.dilated_conv per unit, then the unit's own
 #: BatchNorm2d and LeakyReLU; the first unit and the heads stay stock) whenever ops.context_train_supported accepts the network
@@ -91,6 +96,8 @@ class DenseEstimatorBase(nn.Module):
     def forward(self, x):
         if DENSE_EVAL and (DENSE_EVAL_ALL or self.DENSE_EVAL_BY_DEFAULT or self._stock_passes_4gib(x)) and ops.dense_eval_supported(self, x):
             return ops.dense_eval(self, x)
+        if DENSE_TRAIN and ops.dense_train_supported(self, x):
+            return ops.dense_train(self, x)
         for i in range(self.depth):
             x = torch.cat((getattr(self, "conv_%d" % i)(x), x), 1)
         return self.predict_flow(x)

@@ -2887,6 +2887,193 @@ def dense_eval(net, x):
     return out
 
 
+# ---- EstimatorDenseNet / EstimatorDenseNetSmall in training: forward on the feature buffer, backward in place (csrc/dense_train.hip) ----
+
+#: bytes one feature buffer (and one gradient buffer) of the training route may take: dense_eval_chunks' budget on that route
+DENSE_TRAIN_BUDGET = 4 << 30
+
+
+def _dense_train_chunks(n, h, w, ct):
+    return dense_eval_chunks(n, h, w, ct, budget_bytes=DENSE_TRAIN_BUDGET)
+
+
+def dense_train_supported(net, x):
+    """True if ``net(x)`` of an EstimatorDenseNet / EstimatorDenseNetSmall can run WITH autograd on the kernels of csrc/dense_eval.hip
+    (forward) and csrc/dense_train.hip (backward): autograd enabled, a non-empty CUDA fp32 [N, 5, H, W] input, a
+    model.DenseEstimatorBase with the stock forward (not EstimatorDenseNetTiny), the structure
+    dense_eval_supported asks for (_dense_plan), frame ranges that fit (dense_eval_chunks under DENSE_TRAIN_BUDGET) and every range
+    and layer accepted by dmc_densetrain_supported."""
+    if not torch.is_grad_enabled():
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 5 and x.numel() > 0):
+        return False
+    base = next((c for c in type(net).__mro__ if c.__name__ == "DenseEstimatorBase"), None)
+    if base is None or type(net).forward is not base.forward:     # EstimatorDenseNetTiny has a forward (and kernels) of its own
+        return False
+    plan = _dense_plan(net)
+    if plan is None:
+        return False
+    lay = dense_eval_layout([c.out_channels for c in plan[0]])
+    n, _, h, w = x.shape
+    try:
+        chunks = _dense_train_chunks(n, h, w, lay["ct"])
+    except ValueError:
+        return False
+    lib = _lib.load()
+    sizes = sorted({b - a for a, b in chunks})
+    return all(lib.dmc_densetrain_supported(f, h, w, lay["ct"], k, r) for f in sizes for k, r, _ in lay["layers"] + [lay["head"]])
+
+
+def _dense_weight_grad(dwb, cout, index):
+    """The inverse of _dense_weight for a gradient: ``dwb`` OHWI [r][3][3][k] in buffer order -> [cout, cin, 3, 3] in the module's
+    order (input channel ``index[b]`` from buffer channel b); the pad rows and the pad columns are dropped."""
+    index = index.to(dwb.device)
+    live = (index >= 0).nonzero().reshape(-1)
+    out = torch.empty((cout, 3, 3, int(live.numel())), dtype=dwb.dtype, device=dwb.device)
+    out.index_copy_(3, index[live], dwb[:cout].index_select(3, live))
+    return out.permute(0, 3, 1, 2).contiguous()
+
+
+def _dense_dgrad_blocks(k):
+    """[(c0, cb), ...]: the data gradient's output channels [0, k) in blocks of at most 128, the last padded to a multiple of 32."""
+    return [(c0, min(128, (k - c0 + 31) // 32 * 32)) for c0 in range(0, k, 128)]
+
+
+def _dense_dgrad_packs(wp, k, r):
+    """The transposed, tap-mirrored bf16x3 packs of ``wp`` (OHWI [r][3][3][k], buffer order), one per block of _dense_dgrad_blocks."""
+    lib = _lib.load()
+    packs = []
+    for c0, cb in _dense_dgrad_blocks(k):
+        blk = torch.zeros((r, 3, 3, cb), dtype=torch.float32, device=wp.device)
+        live = min(cb, k - c0)
+        blk[..., :live] = wp[..., c0:c0 + live]
+        pack = torch.empty(lib.dmc_dconv_wpack_bytes(cb, r), dtype=torch.uint8, device=wp.device)
+        _lib.check(lib.dmc_dconv_pack_weights(_lib.ptr(blk), _lib.ptr(pack), cb, r, 1, _stream()), "dmc_dconv_pack_weights")
+        packs.append((c0, cb, pack))
+    return packs
+
+
+class _DenseTrain(torch.autograd.Function):
+    """The dense stack of an EstimatorDenseNet / EstimatorDenseNetSmall over ``x`` and its twelve parameters (w_0, b_0, ..., w_4, b_4,
+    w_head, b_head).  Forward: the launches of dense_eval per frame range; every range's feature buffer is kept.  Backward: per
+    range one gradient buffer of the same layout (csrc/dense_train.hip); the ranges' parameter gradients are added in range order."""
+
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        lib = _lib.load()
+        lay, widths = meta
+        ct = lay["ct"]
+        x = x.contiguous()
+        n, _, h, w = x.shape
+        dev = x.device
+        s = _stream()
+        with _span("dense_train_fwd"):
+            layers = []
+            for i, (k, r, index) in enumerate(lay["layers"]):
+                wp, bp = _dense_weight(_ConvView(params[2 * i], params[2 * i + 1]), k, r, index)
+                pack = torch.empty(lib.dmc_dense_wpack_bytes(k, r), dtype=torch.uint8, device=dev)
+                _lib.check(lib.dmc_dense_pack_weights(_lib.ptr(wp), _lib.ptr(pack), k, r, s), "dmc_dense_pack_weights")
+                layers.append((wp, bp, pack, k, r))
+            hk, _, hindex = lay["head"]
+            hw_, hb = _dense_weight(_ConvView(params[-2], params[-1]), hk, 2, hindex)
+            out = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+            feats = []
+            for a, b in _dense_train_chunks(n, h, w, ct):
+                f = b - a
+                feat = torch.empty((f, h, w, ct), dtype=torch.float32, device=dev)
+                _lib.check(lib.dmc_dense_ingest(_lib.ptr(x[a:b]), _lib.ptr(feat), f, h, w, ct, s), "dmc_dense_ingest")
+                for _, bp, pack, k, r in layers:
+                    _lib.check(lib.dmc_dense_layer_eval(_lib.ptr(feat), _lib.ptr(pack), _lib.ptr(bp), f, h, w, ct, k, r, s), "dmc_dense_layer_eval")
+                _lib.check(lib.dmc_dense_head_eval(_lib.ptr(feat), _lib.ptr(hw_), _lib.ptr(hb), _lib.ptr(out[a:b]), f, h, w, ct, hk, s),
+                           "dmc_dense_head_eval")
+                feats.append((a, b, feat))
+        ctx.dense = (lay, widths, feats, [(wp, k, r) for wp, _, _, k, r in layers], hw_, (n, h, w))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.load()
+        lay, widths, feats, layers, hw_, (n, h, w) = ctx.dense
+        ct = lay["ct"]
+        dout = dout.contiguous()
+        dev = dout.device
+        s = _stream()
+        need_dx = ctx.needs_input_grad[0]
+        depth = len(layers)
+        with _span("dense_train_bwd"):
+            packs = [_dense_dgrad_packs(wp, k, r) if (i > 0 or need_dx) else None for i, (wp, k, r) in enumerate(layers)]
+            dx = torch.empty((n, 5, h, w), dtype=torch.float32, device=dev) if need_dx else None
+            total = None
+            for a, b, feat in feats:
+                f = b - a
+                G = torch.empty((f, h, w, ct), dtype=torch.float32, device=dev)
+                dws = [torch.empty((r, 3, 3, k), dtype=torch.float32, device=dev) for _, k, r in layers]
+                dbs = [torch.empty((r,), dtype=torch.float32, device=dev) for _, _, r in layers]
+                dwh = torch.empty((2, 3, 3, ct), dtype=torch.float32, device=dev)
+                dbh = torch.empty((2,), dtype=torch.float32, device=dev)
+                dpart = dout[a:b]
+                _lib.check(lib.dmc_densetrain_head_dgrad(_lib.ptr(dpart), _lib.ptr(hw_), _lib.ptr(G), f, h, w, ct, s), "dmc_densetrain_head_dgrad")
+                work = torch.empty(lib.dmc_densetrain_head_workspace_bytes(f, h, w, ct), dtype=torch.uint8, device=dev)
+                _lib.check(lib.dmc_densetrain_head_wgrad(_lib.ptr(dpart), _lib.ptr(feat), _lib.ptr(dwh), _lib.ptr(dbh), _lib.ptr(work), f, h, w, ct, s),
+                           "dmc_densetrain_head_wgrad")
+                for i in range(depth - 1, -1, -1):
+                    _, k, r = layers[i]
+                    work = torch.empty(lib.dmc_densetrain_mask_workspace_bytes(f, h, w, r), dtype=torch.uint8, device=dev)
+                    _lib.check(lib.dmc_densetrain_mask(_lib.ptr(feat), _lib.ptr(G), _lib.ptr(dbs[i]), _lib.ptr(work), f, h, w, ct, k, r, s),
+                               "dmc_densetrain_mask")
+                    work = torch.empty(lib.dmc_densetrain_wgrad_workspace_bytes(f, h, w, k, r), dtype=torch.uint8, device=dev)
+                    _lib.check(lib.dmc_densetrain_layer_wgrad(_lib.ptr(feat), _lib.ptr(G), _lib.ptr(dws[i]), _lib.ptr(work), f, h, w, ct, k, r, s),
+                               "dmc_densetrain_layer_wgrad")
+                    del work
+                    if packs[i] is not None:
+                        for c0, cb, pack in packs[i]:
+                            _lib.check(lib.dmc_densetrain_layer_dgrad(_lib.ptr(G), _lib.ptr(pack), f, h, w, ct, k, r, c0, cb, s),
+                                       "dmc_densetrain_layer_dgrad")
+                if need_dx:
+                    _lib.check(lib.dmc_densetrain_export(_lib.ptr(G), _lib.ptr(dx[a:b]), f, h, w, ct, s), "dmc_densetrain_export")
+                del G
+                part = dws + dbs + [dwh, dbh]
+                if total is None:
+                    total = part
+                else:                                              # the ranges in order
+                    for t, p in zip(total, part):
+                        t.add_(p)
+            ctx.dense = None
+            dws, dbs, dwh, dbh = total[:depth], total[depth:2 * depth], total[-2], total[-1]
+            grads = []
+            for i, (_, _, index) in enumerate(lay["layers"]):
+                grads.append(_dense_weight_grad(dws[i], widths[i], index))
+                grads.append(dbs[i][:widths[i]].clone())
+            grads.append(_dense_weight_grad(dwh, 2, lay["head"][2]))
+            grads.append(dbh)
+        return (dx, None) + tuple(g if ctx.needs_input_grad[2 + j] else None for j, g in enumerate(grads))
+
+
+class _ConvView(object):
+    """What _dense_weight reads of a convolution, for a (weight, bias) pair that is not a module's."""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias, self.out_channels = weight, bias, int(weight.shape[0])
+
+
+def dense_train(net, x):
+    """``net(x)`` of an EstimatorDenseNet / EstimatorDenseNetSmall (-> gen_flow [N, 2, H, W]) with autograd, as ONE
+    torch.autograd.Function over ``x`` and the twelve parameters: the forward is dense_eval's launches per frame range with every
+    range's feature buffer kept; the backward (csrc/dense_train.hip) runs in a second buffer of the same layout -- head, then per
+    layer the LeakyReLU mask with the bias gradient, the weight gradient and the in-place data gradient -- without a concatenation,
+    a saved pre-activation or an atomic.  Raises DmcHipError unless dense_train_supported(net, x): never a silent fall-back."""
+    if not dense_train_supported(net, x):
+        raise _lib.DmcHipError("dense_train: the network or the input is not served by the training kernels (dense_train_supported)")
+    convs, head = _dense_plan(net)
+    widths = [c.out_channels for c in convs]
+    lay = dense_eval_layout(widths)
+    params = []
+    for c in convs + [head]:
+        params += [c.weight, c.bias]
+    return _DenseTrain.apply(x, (lay, widths), *params)
+
+
 # ---- ContextNetwork / ContextNetworkAtt in training: the dilated convolutions of the middle units (csrc/dconv.hip) ----
 
 def _dconv_geom_ok(x, cin, cout, dilation):

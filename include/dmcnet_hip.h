@@ -1000,6 +1000,45 @@ int dmc_dense_layer_eval(float* feat, const void* wpack, const float* bias, int 
 int dmc_dense_head_eval(const float* feat, const float* w, const float* bias, float* out_nchw, int N, int H, int W, int CT, int K,
                         dmc_stream_t stream);
 
+/* ---- EstimatorDenseNet / EstimatorDenseNetSmall in training: the backward on the feature buffer (csrc/dense_train.hip) ----
+ * Replaces: autograd's backward of the dense stack above (code/dmcnet/model.py:122-170) -- five concatenations, six convolutions and
+ *           five LeakyReLUs with every intermediate saved -- given the feature buffer feat [N][H][W][CT] the forward (dmc_dense_ingest,
+ *           dmc_dense_layer_eval x 5, dmc_dense_head_eval) left behind.  G [N][H][W][CT] fp32, same layout, holds dL/d(feat).
+ *           (The prefix is dmc_densetrain_, not dmc_dense_train_: the names under dmc_dense_ are the eval route's and are pinned.)
+ * dmc_densetrain_supported: dmc_dense_supported(N, H, W, CT, K, R), and for the head (R == 2) K == CT <= 512.
+ * dmc_densetrain_*_workspace_bytes: the bytes the entry point of that name uses of `workspace` (per-range / per-workgroup partial
+ *   sums); 0 for an unsupported shape.  mask: ceil(NHW / 1024) * R * 4.  wgrad: ranges * R * 9 * K * 4, ranges as in
+ *   dmc_dconv_wgrad (32-pixel steps, at most 256 steps a range, 64 ranges when that allows).  head: ranges * (18 CT + 2) * 4.
+ * dmc_densetrain_head_dgrad: G[m][c] = sum_t sum_co dout[m - o(t)][co] w[co][t][c] for every c < CT (w [2][3][3][CT], buffer order;
+ *   dout NCHW [N][2][H][W]): writes EVERY float of G; fp32 FMAs in a fixed order.
+ * dmc_densetrain_head_wgrad: dw [2][3][3][CT] = sum_m dout[m][co] feat[m + o(t)][c], db [2] = sum_m dout[m][co]; fp32 FMAs, pixels in
+ *   order within a range, ranges in order.
+ * dmc_densetrain_mask: G[.][K + r] <- feat[.][K + r] > 0 ? g : 0.1f * g in place for r < R, db [R] = the sums of the result over the
+ *   pixels.  Every other channel of G is left as it is; feat is read only.
+ * dmc_densetrain_layer_wgrad: dw OHWI [R][3][3][K] (buffer order) = sum_m G[m][K + r] feat[m + o(t)][c]; bf16x3 arithmetic on the
+ *   matrix cores, at most 8 k pixels per fp32 accumulation.  Reads feat channels [0, K) and G channels [K, K + R) only.
+ * dmc_densetrain_layer_dgrad: G[m][c] += sum_t sum_r G[m - o(t)][K + r] w[r][t][c] in place for c0 <= c < min(c0 + cb, K): one block
+ *   of at most 128 channels a call.  wpack_t = dmc_dconv_pack_weights(w[:, :, :, c0 : c0 + cb] (zero columns from K on) as
+ *   OHWI [R][3][3][cb], cb, R, transposed = 1); cb in {32, 64, 96, 128}, c0 % 16 == 0, c0 < K, c0 + cb <= K + 16.  Reads channels
+ *   [K, K + R) only, writes the block only; bf16x3 arithmetic on the matrix cores.
+ * dmc_densetrain_export: dx NCHW [N][5][H][W] = G[.][0, 5).
+ * Deterministic, no atomics; the caller owns every buffer; nothing allocates or synchronises.
+ * DMC_E_INVALID before any launch (nothing written): a NULL pointer, an unsupported shape. */
+int dmc_densetrain_supported(int N, int H, int W, int CT, int K, int R);
+size_t dmc_densetrain_mask_workspace_bytes(int N, int H, int W, int R);
+size_t dmc_densetrain_wgrad_workspace_bytes(int N, int H, int W, int K, int R);
+size_t dmc_densetrain_head_workspace_bytes(int N, int H, int W, int CT);
+int dmc_densetrain_head_dgrad(const float* dout_nchw, const float* w, float* G, int N, int H, int W, int CT, dmc_stream_t stream);
+int dmc_densetrain_head_wgrad(const float* dout_nchw, const float* feat, float* dw, float* db, void* workspace, int N, int H, int W,
+                              int CT, dmc_stream_t stream);
+int dmc_densetrain_mask(const float* feat, float* G, float* db, void* workspace, int N, int H, int W, int CT, int K, int R,
+                        dmc_stream_t stream);
+int dmc_densetrain_layer_wgrad(const float* feat, const float* G, float* dw_ohwi, void* workspace, int N, int H, int W, int CT, int K,
+                               int R, dmc_stream_t stream);
+int dmc_densetrain_layer_dgrad(float* G, const void* wpack_t, int N, int H, int W, int CT, int K, int R, int c0, int cb,
+                               dmc_stream_t stream);
+int dmc_densetrain_export(const float* G, float* dx_nchw, int N, int H, int W, int CT, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
