@@ -1,9 +1,12 @@
-// Device code shared by the dilated 3x3 gather convolutions (ctx_eval.hip: conv + BatchNorm + LeakyReLU in eval mode; dconv.hip:
-// the raw convolution of the training route, forward and data gradient); gfx950 only.
+// Device code shared by the 3x3 gather convolutions; gfx950 only.  Users: ctx_eval.hip (conv + BatchNorm + LeakyReLU in eval mode),
+// dconv.hip (the raw dilated convolution of the training route, forward and data gradient), dense_eval.hip (a layer of the dense
+// estimators, in place on the feature buffer) and dense_train.hip (that layer's data gradient).
 //
-// gather_gemm<TN, TM> is the main loop of both: the per-lane activation gather with the 9-bit tap mask, the double-buffered
-// weight panel in LDS, the six bf16x3 slice products in one fixed order.  What happens to the accumulators afterwards (the
-// epilogue) is the caller's.  pack_kernel writes the weight panels the loop reads, in either orientation.
+// gather_gemm<TN, TM> is the ONE main loop of all four: the per-lane activation gather with the 9-bit tap mask, the
+// double-buffered weight panel in LDS, the six bf16x3 slice products in one fixed order.  What it reads it asks of the kernel's
+// own argument struct (GatherArgs, DenseArgs: the view); what happens to the accumulators afterwards (the epilogue) is the
+// caller's.  pack_kernel writes the weight panels the loop reads, in either orientation.  What the weight gradients of the same
+// routes share is in ctx_wgrad.h.
 #pragma once
 #include "dmc_common.h"
 
@@ -14,6 +17,12 @@ struct GatherArgs {
     const float* x;                 // [N][H][W][Cin]
     const unsigned short* wpack;    // [9][Cin / 16][3][Cout][16] bf16
     int N, H, W, Cin, d, M;         // M = N H W
+    // the view gather_gemm reads: pixel stride = contraction length = Cin, from channel 0, at dilation d
+    __device__ const float* base() const { return x; }
+    __device__ int stride() const { return Cin; }
+    __device__ int length() const { return Cin; }
+    __device__ int first() const { return 0; }
+    __device__ int dilation() const { return d; }
 };
 
 template <int TN>
@@ -23,13 +32,16 @@ struct GatherLds {
     static constexpr int BYTES = 2 * CH;
 };
 
+// The view V: channels [first(), first() + length()) of pixel rows that are stride() floats apart, from base(), at dilation();
+// H, W, M and wpack [9][length() / 16][3][32 TN][16] bf16 by these names.  It is the kernel's argument struct, read in place.
+//
 // GEMM view: rows = output channels (A operand = weight slices), columns = output pixels (B operand = the input at the
-// tap-shifted pixel), K = (tap, ci) in k-blocks of 16 channels.  A workgroup of four waves (256 threads) owns 128 TM
+// tap-shifted pixel), contraction = (tap, channel) in k-blocks of 16 channels.  A workgroup of four waves (256 threads) owns 128 TM
 // consecutive pixels from blockIdx.x * 128 TM; the wave owns 32 TM of them, from m0 (returned), and all 32 TN channels.
 // On return the lane holds pixel m0 + 32 i + (lane & 31), channels 32 j + 8 gq + 4 (lane >> 5) + e in acc[i][j][4 gq + e].
 // lds: GatherLds<TN>::BYTES bytes, 16-byte aligned.
-template <int TN, int TM>
-__device__ __forceinline__ int gather_gemm(const GatherArgs& a, char* lds, f32x16 (&acc)[TM][TN]) {
+template <int TN, int TM, class V>
+__device__ __forceinline__ int gather_gemm(const V& a, char* lds, f32x16 (&acc)[TM][TN]) {
     constexpr int COUT = GatherLds<TN>::COUT;
     constexpr int CH = GatherLds<TN>::CH;
     constexpr int NWR = (CH + 4095) / 4096;                // 16-byte pieces per thread
@@ -39,7 +51,7 @@ __device__ __forceinline__ int gather_gemm(const GatherArgs& a, char* lds, f32x1
     const int l31 = lane & 31, khalf = lane >> 5;
     const int m0 = blockIdx.x * (128 * TM) + wave * (32 * TM);
 
-    // ---- this lane's pixels: offset of (n, y, x, 8 khalf) and the taps that fall inside the frame ----
+    // ---- this lane's pixels: offset of (n, y, x, first() + 8 khalf) and the taps that fall inside the frame ----
     long xbase[TM];
     unsigned tmask[TM];
 #pragma unroll
@@ -50,27 +62,28 @@ __device__ __forceinline__ int gather_gemm(const GatherArgs& a, char* lds, f32x1
             const int hw = a.H * a.W;
             const int rem = m % hw;
             const int yy = rem / a.W, xx = rem - yy * a.W;
-            xbase[i] = (long)m * a.Cin + 8 * khalf;
+            xbase[i] = (long)m * a.stride() + a.first() + 8 * khalf;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
-                const int iy = yy + (t / 3 - 1) * a.d, ix = xx + (t % 3 - 1) * a.d;
+                const int iy = yy + (t / 3 - 1) * a.dilation(), ix = xx + (t % 3 - 1) * a.dilation();
                 if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) tmask[i] |= 1u << t;
             }
         }
     }
 
-    const int nkb = a.Cin >> 4;
+    const int nkb = a.length() >> 4;
     const int nsteps = 9 * nkb;
     int tap = 0, kb = 0;                                   // of the step being LOADED
     f32x4 xlo[TM], xhi[TM];
     u32x4 wr[NWR];
     auto load_step = [&](int s) {
-        const int dy = (tap / 3 - 1) * a.d, dx = (tap % 3 - 1) * a.d;
-        const long toff = ((long)dy * a.W + dx) * a.Cin + 16 * kb;
+        const int dy = (tap / 3 - 1) * a.dilation(), dx = (tap % 3 - 1) * a.dilation();
+        const long toff = ((long)dy * a.W + dx) * a.stride() + 16 * kb;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const bool ok = (tmask[i] >> tap) & 1;
-            const float* p = a.x + (ok ? xbase[i] + toff : 0);
+            // (a masked lane reads the first 16 gathered channels of pixel 0)
+            const float* p = a.base() + (ok ? xbase[i] + toff : (long)a.first());
             const f32x4 lo = *reinterpret_cast<const f32x4*>(p), hi = *reinterpret_cast<const f32x4*>(p + 4);
             xlo[i] = ok ? lo : (f32x4){0.f, 0.f, 0.f, 0.f};
             xhi[i] = ok ? hi : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -159,4 +172,24 @@ inline bool middle_ok(int Cin, int Cout, int d) { return width_ok(Cin) && width_
 inline bool index_ok(int N, int H, int W) { return N > 0 && H > 0 && W > 0 && (long long)N * H * W * 128 < (1ll << 31); }
 
 }  // namespace ctxk
+
+namespace densek {
+
+// kernel arguments of dense_eval.hip's layer and dense_train.hip's data gradient of a layer
+struct DenseArgs {
+    float* feat;                    // [M][CT]; gathered in [koff, koff + K), written by the caller's epilogue
+    const unsigned short* wpack;    // [9][K / 16][3][32 TN][16] bf16
+    const float* bias;              // [32 TN] (the forward's epilogue; unused by the data gradient)
+    int H, W, CT, K, M;             // M = N H W
+    int koff;                       // first gathered channel: 0 in the forward, the layer's slot in the data gradient
+    int c0, cend;                   // the data gradient's output channels: [c0, c0 + 32 TN), stored below cend
+    // the view gather_gemm reads: pixel stride CT, contraction length K from channel koff, dilation 1
+    __device__ const float* base() const { return feat; }
+    __device__ int stride() const { return CT; }
+    __device__ int length() const { return K; }
+    __device__ int first() const { return koff; }
+    __device__ int dilation() const { return 1; }
+};
+
+}  // namespace densek
 }  // namespace dmc

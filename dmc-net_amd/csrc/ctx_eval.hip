@@ -9,10 +9,11 @@
 //   head(s)     (32 -> 2, d = 1)     NHWC in, NCHW out; predict_flow and predict_att (+ ReLU) of the attention network
 //                                    in one launch over the same input
 //
-// Middle kernel.  GEMM view: rows = output channels (A operand = weight slices), columns = output pixels (B operand = the
-// input at the tap-shifted pixel), K = (tap, ci) in k-blocks of 16 channels.  Dilation enters through the tap offsets
-// only: tap (ky, kx) reads pixel (y + (ky - 1) d, x + (kx - 1) d), zero outside the H x W frame (tested per coordinate,
-// never on a linearised offset).
+// Middle kernel = ctx_common.h's gather_gemm (the one main loop of this file, dconv.hip, dense_eval.hip and
+// dense_train.hip's data gradient; what follows describes it for all of them) + this file's epilogue.  GEMM view: rows =
+// output channels (A operand = weight slices), columns = output pixels (B operand = the input at the tap-shifted pixel),
+// K = (tap, ci) in k-blocks of 16 channels.  Dilation enters through the tap offsets only: tap (ky, kx) reads pixel
+// (y + (ky - 1) d, x + (kx - 1) d), zero outside the H x W frame (tested per coordinate, never on a linearised offset).
 //   * A workgroup of four waves owns 128 TM consecutive pixels; each wave owns 32 TM of them and ALL Cout = 32 TN
 //     channels (TN accumulator tiles of 32 x 32 per pixel tile).  Cout = 96 and 32 are simply TN = 3 and 1: no padded
 //     channel is computed, stored or allocated.
@@ -50,7 +51,7 @@ __device__ __forceinline__ float bn_leaky(float v, float mean, float istd, float
     return t > 0.f ? t : SLOPE * t;
 }
 
-// main loop: ctx_common.h's gather_gemm (shared with the raw convolution of dconv.hip); the epilogue is this kernel's
+// main loop: ctx_common.h's gather_gemm with stride = length = Cin from channel 0; the epilogue is this kernel's
 template <int TN, int TM>
 __global__ __launch_bounds__(256) void ctx_unit_kernel(CtxArgs a) {
     constexpr int COUT = 32 * TN;

@@ -3,18 +3,18 @@
 //   Conv2d(Cin, Cout, 3, stride 1, padding d, dilation d, bias=False),   Cin, Cout in {32, 64, 96, 128}, d in {1, 2, 4, 8, 16}
 // over NHWC fp32 tensors.  BatchNorm and LeakyReLU stay with their modules; this file replaces the convolutions only.
 //
-// dconv_fwd_kernel.  ctx_common.h's gather_gemm (the main loop of ctx_eval.hip's unit kernel: per-lane gather with the 9-bit
-// tap mask, double-buffered weight panel in LDS, six bf16x3 slice products per fp32 product on v_mfma_f32_32x32x16_bf16) with a
-// raw epilogue: one 16-byte store per accumulator quad.  With stride 1 and padding = dilation the DATA GRADIENT is the same
+// dconv_fwd_kernel.  ctx_common.h's gather_gemm (the main loop of ctx_eval.hip's unit kernel, described there) with a raw
+// epilogue: one 16-byte store per accumulator quad.  With stride 1 and padding = dilation the DATA GRADIENT is the same
 // convolution: dx[p][ci] = sum over (t, co) of dy[p + o(t)][co] w[co][8 - t][ci], because o(8 - t) = -o(t) -- so the caller
 // packs the weights transposed (pack_kernel, transposed = 1) and calls the same entry point with Cin and Cout exchanged.
 //
 // dconv_wgrad_kernel.  dw[co][t][ci] = sum over pixels p of dy[p][co] x[p + o(t)][ci], the pixels whose tap lies inside the
 // frame (tested per coordinate, never on a linearised offset).  A GEMM over PIXELS (K) while both tensors are channel-contiguous:
-//   * grid = (pixel ranges, 9 taps).  wgrad_plan: steps = ceil(N H W / 32) are dealt to min(steps, 64) ranges, a range is capped
-//     at 256 steps (8 k pixels: the length of one fp32 accumulation), ranges = ceil(steps / per_range).  A workgroup of four
-//     waves owns the whole [Cout][Cin] block of its tap -- up to sixteen
-//     32 x 32 tiles, tile q of the block with wave q % 4, at most four per wave (64 accumulator registers) -- over its range.
+//   * grid = (pixel ranges, 9 taps).  wgrad_plan (ctx_wgrad.h, with the constants and the reduce; dense_train.hip shares them):
+//     steps = ceil(N H W / 32) are dealt to min(steps, 64) ranges, a range is capped at 256 steps (8 k pixels: the length of
+//     one fp32 accumulation), ranges = ceil(steps / per_range).  A workgroup of four waves owns the whole [Cout][Cin] block of its
+//     tap -- up to sixteen 32 x 32 tiles, tile q of the block with wave q % 4, at most four per wave (64 accumulator registers) --
+//     over its range.
 //   * a step is KP = 32 pixels: the workgroup loads dy[32][Cout] and the tap-shifted x[32][Cin] (zeros where the tap leaves the
 //     frame or the pixel is past the tensor) into registers one step ahead, splits each value into its three bf16 slices ONCE and
 //     stores them as chunk planes [slice][16-channel chunk][pixel][16] (32 bytes per pixel, 16-byte writes).  Plane stride
@@ -22,10 +22,10 @@
 //     apart, four consecutive pixels are 128 contiguous bytes -- the layout of x3s_wgrad_kernel (conv_x3s.hip).
 //   * fragments leave the LDS transposed (ds_read_b64_tr_b16, two reads = the eight consecutive pixels of an operand row);
 //     every wave executes them with all lanes (the tile test is wave-uniform).
-//   * partial sums [range][Cout][9][Cin] go to the caller's workspace; dconv_wgrad_reduce_kernel adds the ranges in order.
+//   * partial sums [range][Cout][9][Cin] go to the caller's workspace; ordered_reduce_kernel adds the ranges in order.
 // No atomics anywhere: results are bit-identical from run to run.  All tensor offsets are 64-bit; dmc_dconv_supported bounds
 // N H W 128 below 2^31 so that pixel indices fit an int.
-#include "ctx_common.h"
+#include "ctx_wgrad.h"
 
 using namespace dmc;
 using namespace dmc::ctxk;
@@ -63,14 +63,6 @@ __global__ __launch_bounds__(256) void dconv_fwd_kernel(FwdArgs a) {
 }
 
 // ---- weight gradient ---------------------------------------------------------------------------------------------------
-constexpr int KP = 32;                       // pixels per step
-constexpr int PLANE = KP * 32 + 128;         // bytes between chunk planes: = 128 (mod 256)
-constexpr int NCHUNK = 8;                    // 16-channel chunks of the widest tensor (128 channels)
-constexpr int TILE_BYTES = 3 * NCHUNK * PLANE;
-constexpr int MAX_RANGES = 64;               // pixel ranges of a small tensor (x 9 taps workgroups)
-constexpr int MAX_RANGE_STEPS = 256;         // ... and of a large one: a range is at most 8 k pixels, so that one fp32 accumulator
-                                             // never carries a longer sum (42 x 448^2 in 64 ranges of 131 k pixels: 1.4e-5 off)
-
 struct WgArgs {
     const float* x;                 // [N][H][W][Cin]
     const float* dy;                // [N][H][W][Cout]
@@ -78,18 +70,6 @@ struct WgArgs {
     int H, W, Cin, Cout, d, M;
     int steps_per_range, steps;
 };
-
-struct WgPlan { int steps, ranges, per_range; };
-WgPlan wgrad_plan(int N, int H, int W) {
-    WgPlan p;
-    const int M = N * H * W;
-    p.steps = (M + KP - 1) / KP;
-    int r = p.steps < MAX_RANGES ? p.steps : MAX_RANGES;
-    p.per_range = (p.steps + r - 1) / r;
-    if (p.per_range > MAX_RANGE_STEPS) p.per_range = MAX_RANGE_STEPS;
-    p.ranges = (p.steps + p.per_range - 1) / p.per_range;
-    return p;
-}
 
 __global__ __launch_bounds__(256) void dconv_wgrad_kernel(WgArgs a) {
     __shared__ __attribute__((aligned(1024))) char lds[2 * TILE_BYTES];        // dy tile | x tile
@@ -227,19 +207,6 @@ __global__ __launch_bounds__(256) void dconv_wgrad_kernel(WgArgs a) {
     }
 }
 
-// dw = the ranges' partials added in range order; one thread per four consecutive elements
-__global__ __launch_bounds__(256) void dconv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int ranges, int numel) {
-    const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= numel) return;
-    f32x4 s = *reinterpret_cast<const f32x4*>(part + i);
-    for (int k = 1; k < ranges; ++k) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(part + (size_t)k * numel + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] += v[e];
-    }
-    *reinterpret_cast<f32x4*>(dw + i) = s;
-}
-
 }  // namespace
 
 extern "C" {
@@ -299,8 +266,8 @@ int dmc_dconv_wgrad(const float* x, const float* dy, float* dw_ohwi, void* works
     dconv_wgrad_kernel<<<dim3(p.ranges, 9), 256, 0, s>>>(a);
     const int rc = check_launch("dmc_dconv_wgrad");
     if (rc) return rc;
-    const int numel = Cout * 9 * Cin;
-    dconv_wgrad_reduce_kernel<<<(numel / 4 + 255) / 256, 256, 0, s>>>(a.part, dw_ohwi, p.ranges, numel);
+    const long numel = (long)Cout * 9 * Cin;
+    ordered_reduce_kernel<<<(int)((numel + 255) / 256), 256, 0, s>>>(a.part, dw_ohwi, p.ranges, numel);
     return check_launch("dmc_dconv_wgrad");
 }
 

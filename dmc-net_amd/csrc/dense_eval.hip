@@ -7,9 +7,9 @@
 //
 //   ingest  x NCHW [N][5][H][W] -> feat[m][0..16): one thread per pixel, four 16-byte stores
 //   layer   feat[m][K..K+R) = leaky(conv3x3(feat[.][0..K)) + bias): implicit GEMM over (tap, channel) on v_mfma_f32_32x32x16_bf16 in
-//           the bf16x3 arithmetic of ctx_common.h's gather_gemm -- the same loop with the contraction length K and the pixel
-//           stride CT as two numbers (gather_gemm has one, Cin, for both), dilation 1: dense_common.h's dense_gemm, which the
-//           training route's data gradient shares (dense_train.hip)
+//           the bf16x3 arithmetic: ctx_common.h's gather_gemm (the loop of ctx_eval.hip and dconv.hip) with the pixel stride
+//           CT, the contraction length K, the first gathered channel 0 and dilation 1; the training route's data gradient
+//           (dense_train.hip) is the same loop from channel K
 //   head    predict_flow (K -> 2, no activation), NCHW out: plain fp32 FMAs in the form of ctx_eval.hip's ctx_heads_kernel
 //   pack    ctxk::pack_kernel as it is, on the padded OHWI weight [R][3][3][K]: panels [9][K / 16][3][R][16] bf16
 //
@@ -18,17 +18,13 @@
 // buffer, so no workgroup can observe another's stores, whatever the order in which tiles run -- there is no race and nothing to
 // synchronise.  (K + R <= CT keeps the stores inside the pixel's row; K % 16 == 0 keeps every gather below K.)
 //
-// Layer kernel.  GEMM view: rows = output channels (A operand = weight slices), columns = output pixels (B operand = the
-// prefix at the tap-shifted pixel), contraction = (tap, channel) in k-blocks of 16 channels; a tap outside the H x W frame is zero
-// (tested per coordinate, never on a linearised offset).  Four waves own 128 TM consecutive pixels, each wave 32 TM of them and
-// all R = 32 TN channels.  Per lane and step: two 16-byte gathers per pixel one step ahead, split into three bf16 slices in
-// registers; the step's weight chunk (three slices of [R][16] bf16, 96 R bytes) goes global -> registers -> LDS one step ahead
-// (two buffers, one barrier per step).  The six slice products are issued in the fixed order (w slice, x slice) =
-// (0,2) (0,1) (0,0) | (1,1) (1,0) | (2,0).  Epilogue: v = acc + bias[co]; v > 0 ? v : 0.1f v; one 16-byte store per channel quad.
+// Layer kernel.  The main loop, its ownership of pixels and channels and the order of the six slice products are gather_gemm's
+// (described in ctx_common.h and ctx_eval.hip's header); the B operand is the prefix at the tap-shifted pixel.
+// Epilogue: v = acc + bias[co]; v > 0 ? v : 0.1f v; one 16-byte store per channel quad.
 // No atomics; a pixel's sum is formed in one fixed order by one lane column of the matrix core whatever tile or batch the
 // pixel is in: results are bit-identical from run to run and independent of the batch.
 // All tensor offsets are 64-bit; dmc_dense_supported() bounds N H W CT below 2^31 so that the pixel index fits an int.
-#include "dense_common.h"
+#include "ctx_common.h"
 
 using namespace dmc;
 using namespace dmc::ctxk;
@@ -43,7 +39,7 @@ template <int TN, int TM>
 __global__ __launch_bounds__(256) void dense_layer_kernel(DenseArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[GatherLds<TN>::BYTES];
     f32x16 acc[TM][TN];
-    const int m0 = dense_gemm<TN, TM>(a, lds, acc);
+    const int m0 = gather_gemm<TN, TM>(a, lds, acc);
     const int lane = threadIdx.x & 63;
     const int l31 = lane & 31, khalf = lane >> 5;
 
@@ -131,8 +127,7 @@ __global__ __launch_bounds__(256) void dense_head_kernel(const float* __restrict
     }
 }
 
-bool layer_width_ok(int R) { return R == 32 || R == 64 || R == 96 || R == 128; }
-bool pack_ok(int K, int R) { return K >= 16 && K % 16 == 0 && layer_width_ok(R) && (long long)K * R * 9 < (1ll << 31); }
+bool pack_ok(int K, int R) { return K >= 16 && K % 16 == 0 && width_ok(R) && (long long)K * R * 9 < (1ll << 31); }
 
 }  // namespace
 
@@ -142,7 +137,7 @@ int dmc_dense_supported(int N, int H, int W, int CT, int K, int R) {
     if (N <= 0 || H <= 0 || W <= 0 || CT <= 0 || CT % 4 != 0 || K < 16 || K % 16 != 0) return 0;
     if ((long long)N * H * W * CT >= (1ll << 31)) return 0;
     if (R == 2) return (K <= CT && K <= HEAD_KMAX && K % 4 == 0) ? 1 : 0;
-    return (layer_width_ok(R) && (long long)K + R <= CT) ? 1 : 0;
+    return (width_ok(R) && (long long)K + R <= CT) ? 1 : 0;
 }
 
 size_t dmc_dense_wpack_bytes(int K, int R) {

@@ -15,14 +15,15 @@
 //   mask         G[m][K + r] <- feat[m][K + r] > 0 ? g : 0.1f g in place (pad channels: feat = 0, g = 0, stay 0); the bias
 //                gradient db_k[r] = sum_m of the masked value from the same pass: per thread over its pixels in order, the
 //                workgroup's threads in order, per-workgroup partials, an ordered final reduce.
-//   wgrad        dW_k[r][t][c] = sum_m G[m][K + r] feat[m + o(t)][c], c < K, buffer order: dconv.hip's dconv_wgrad_kernel (bf16x3,
-//                the six slice products smallest first, 32-pixel steps, ranges of at most 256 steps = 8 k pixels per fp32
-//                accumulation, partials to the caller's workspace, ordered reduce) with both operands at pixel stride CT, at
-//                channel offsets K and 0, and a third grid dimension over 128-channel blocks of c (a workgroup owns at most 128
-//                input channels).  K = 16 + 32 n: the last 32-channel tile of the last block has 16 live columns; its other 16 are
-//                staged as zeros and never stored.  No read leaves the pixel's row of CT floats, no store leaves dW.
+//   wgrad        dW_k[r][t][c] = sum_m G[m][K + r] feat[m + o(t)][c], c < K, buffer order: a copy of dconv.hip's
+//                dconv_wgrad_kernel with ctx_wgrad.h's wgrad_plan, constants and reduce (bf16x3, the six slice products smallest
+//                first, 32-pixel steps, ranges of at most 256 steps = 8 k pixels per fp32 accumulation, partials to the caller's
+//                workspace, ordered reduce) with both operands at pixel stride CT, at channel offsets K and 0, and a third grid
+//                dimension over 128-channel blocks of c (a workgroup owns at most 128 input channels).  K = 16 + 32 n: the last
+//                32-channel tile of the last block has 16 live columns; its other 16 are staged as zeros and never stored.  No
+//                read leaves the pixel's row of CT floats, no store leaves dW.
 //   dgrad        G[m][c] += sum_t sum_r G[m - o(t)][K + r] W_k[r][t][c], c < K (skipped for k = 0 unless x needs a gradient):
-//                dense_common.h's dense_gemm on the transposed, tap-mirrored pack (ctxk::pack_kernel, transposed = 1) of a block
+//                ctx_common.h's gather_gemm on the transposed, tap-mirrored pack (ctxk::pack_kernel, transposed = 1) of a block
 //                of at most 128 output channels; contraction length R at channel offset K; one launch per block, the last one
 //                masked to c < K at the store.
 //   export       slot 0's five live channels of G -> dx NCHW.
@@ -37,7 +38,7 @@
 //
 // No atomics anywhere: results are bit-identical from run to run.  All tensor offsets are 64-bit; dmc_densetrain_supported()
 // bounds N H W CT below 2^31 so that the pixel index fits an int.  The caller owns every buffer; nothing allocates or synchronises.
-#include "dense_common.h"
+#include "ctx_wgrad.h"
 
 using namespace dmc;
 using namespace dmc::ctxk;
@@ -48,35 +49,6 @@ namespace {
 constexpr float SLOPE = 0.1f;
 constexpr int HEAD_CTMAX = 512;              // 72 CT bytes of LDS hold the head's weight
 constexpr int MASK_PIX = 1024;               // pixels per workgroup of the mask pass
-
-// ---- pixel ranges of the weight gradients: dconv.hip's wgrad_plan ----
-constexpr int KP = 32;                       // pixels per step
-constexpr int PLANE = KP * 32 + 128;         // bytes between chunk planes: = 128 (mod 256)
-constexpr int NCHUNK = 8;                    // 16-channel chunks of the widest operand (128 channels)
-constexpr int TILE_BYTES = 3 * NCHUNK * PLANE;
-constexpr int MAX_RANGES = 64;               // pixel ranges of a small tensor
-constexpr int MAX_RANGE_STEPS = 256;         // ... and of a large one: at most 8 k pixels per fp32 accumulation
-
-struct WgPlan { int steps, ranges, per_range; };
-WgPlan wgrad_plan(int N, int H, int W) {
-    WgPlan p;
-    const int M = N * H * W;
-    p.steps = (M + KP - 1) / KP;
-    int r = p.steps < MAX_RANGES ? p.steps : MAX_RANGES;
-    p.per_range = (p.steps + r - 1) / r;
-    if (p.per_range > MAX_RANGE_STEPS) p.per_range = MAX_RANGE_STEPS;
-    p.ranges = (p.steps + p.per_range - 1) / p.per_range;
-    return p;
-}
-
-// out[i] = the partials' element i added in order; one thread per element
-__global__ __launch_bounds__(256) void ordered_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int nparts, long numel) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= numel) return;
-    float s = part[i];
-    for (int k = 1; k < nparts; ++k) s += part[(size_t)k * numel + i];
-    out[i] = s;
-}
 
 // ---- head, data gradient: every float of G.  w [2][9][CT] in LDS (72 CT bytes, dynamic) ----
 __global__ __launch_bounds__(256) void head_dgrad_kernel(const float* __restrict__ dout, const float* __restrict__ w, float* __restrict__ G,
@@ -354,13 +326,13 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgArgs a) {
     }
 }
 
-// ---- layer, data gradient: dense_gemm over G[.][K, K + R) on the transposed pack of output channels [c0, c0 + 32 TN); the
+// ---- layer, data gradient: gather_gemm over G[.][K, K + R) on the transposed pack of output channels [c0, c0 + 32 TN); the
 // epilogue adds into G[m][c], c < cend, of the workgroup's own pixels ----
 template <int TN, int TM>
 __global__ __launch_bounds__(256) void dense_dgrad_kernel(DenseArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[GatherLds<TN>::BYTES];
     f32x16 acc[TM][TN];
-    const int m0 = dense_gemm<TN, TM>(a, lds, acc);
+    const int m0 = gather_gemm<TN, TM>(a, lds, acc);
     const int lane = threadIdx.x & 63;
     const int l31 = lane & 31, khalf = lane >> 5;
 #pragma unroll
@@ -393,8 +365,6 @@ __global__ __launch_bounds__(256) void export_kernel(const float* __restrict__ G
     xp[0] = v[0]; xp[HW] = v[1]; xp[2 * (long)HW] = v[2]; xp[3 * (long)HW] = v[3]; xp[4 * (long)HW] = gp[4];
 }
 
-bool layer_width_ok(int R) { return R == 32 || R == 64 || R == 96 || R == 128; }
-
 }  // namespace
 
 extern "C" {
@@ -406,13 +376,13 @@ int dmc_densetrain_supported(int N, int H, int W, int CT, int K, int R) {
 }
 
 size_t dmc_densetrain_mask_workspace_bytes(int N, int H, int W, int R) {
-    if (N <= 0 || H <= 0 || W <= 0 || !layer_width_ok(R) || (long long)N * H * W >= (1ll << 31)) return 0;
+    if (N <= 0 || H <= 0 || W <= 0 || !width_ok(R) || (long long)N * H * W >= (1ll << 31)) return 0;
     const long long M = (long long)N * H * W;
     return (size_t)((M + MASK_PIX - 1) / MASK_PIX) * R * sizeof(float);
 }
 
 size_t dmc_densetrain_wgrad_workspace_bytes(int N, int H, int W, int K, int R) {
-    if (N <= 0 || H <= 0 || W <= 0 || K < 16 || K % 16 != 0 || !layer_width_ok(R) || (long long)N * H * W >= (1ll << 31)) return 0;
+    if (N <= 0 || H <= 0 || W <= 0 || K < 16 || K % 16 != 0 || !width_ok(R) || (long long)N * H * W >= (1ll << 31)) return 0;
     return (size_t)wgrad_plan(N, H, W).ranges * R * 9 * K * sizeof(float);
 }
 
@@ -485,7 +455,7 @@ int dmc_densetrain_layer_wgrad(const float* feat, const float* G, float* dw_ohwi
 
 int dmc_densetrain_layer_dgrad(float* G, const void* wpack_t, int N, int H, int W, int CT, int K, int R, int c0, int cb, dmc_stream_t stream) {
     if (!G || !wpack_t) return fail(DMC_E_INVALID, "dmc_densetrain_layer_dgrad: null pointer");
-    if (R == 2 || !dmc_densetrain_supported(N, H, W, CT, K, R) || !layer_width_ok(cb) || c0 < 0 || c0 % 16 != 0 || c0 >= K || c0 + cb > K + 16)
+    if (R == 2 || !dmc_densetrain_supported(N, H, W, CT, K, R) || !width_ok(cb) || c0 < 0 || c0 % 16 != 0 || c0 >= K || c0 + cb > K + 16)
         return fail(DMC_E_INVALID, "dmc_densetrain_layer_dgrad: unsupported shape (N %d, H %d, W %d, CT %d, K %d, R %d, c0 %d, cb %d)", N, H, W, CT, K,
                     R, c0, cb);
     DenseArgs a;
