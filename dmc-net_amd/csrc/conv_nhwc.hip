@@ -198,11 +198,12 @@ __global__ __launch_bounds__(256) void conv_nhwc_kernel(ConvArgs a) {
     }
 
     // ---- epilogue: lane holds pixel column i16 of tile i, channels 4*kq .. 4*kq+3 of tile j ----
-    float s1[TN][4], s2[TN][4];
+    // the statistics are fp64 sums of the STORED fp32 values and of their fp64 squares: nothing is rounded on the way
+    double s1[TN][4], s2[TN][4];
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { s1[j][e] = 0.f; s2[j][e] = 0.f; }
+        for (int e = 0; e < 4; ++e) { s1[j][e] = 0.0; s2[j][e] = 0.0; }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + wm * (BM / WM) + 16 * i + i16;
@@ -234,8 +235,10 @@ __global__ __launch_bounds__(256) void conv_nhwc_kernel(ConvArgs a) {
             }
             if (mok) {
                 *reinterpret_cast<float4*>(a.y + opix * a.Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
+                if (a.stat_part) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { s1[j][e] += v[e]; s2[j][e] += v[e] * v[e]; }
+                    for (int e = 0; e < 4; ++e) { const double d = (double)v[e]; s1[j][e] += d; s2[j][e] += d * d; }
+                }
             }
         }
     }
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(256) void conv_nhwc_kernel(ConvArgs a) {
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const double d1 = row16_sum((double)s1[j][e]), d2 = row16_sum((double)s2[j][e]);
+                const double d1 = row16_sum(s1[j][e]), d2 = row16_sum(s2[j][e]);
                 if (i16 == 0) {
                     const int c = wn * (BN / WN) + 16 * j + 4 * kq + e;
                     red[(wm * BN + c) * 2 + 0] = d1;
@@ -310,9 +313,9 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvArgs& a, f32x16 (&a
     if (a.stat_part) __syncthreads();                         // every wave is done with the operand tiles
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        float s1[16], s2[16];
+        double s1[16], s2[16];                                // fp64 sums of the STORED fp32 values and of their fp64 squares
 #pragma unroll
-        for (int e = 0; e < 16; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+        for (int e = 0; e < 16; ++e) { s1[e] = 0.0; s2[e] = 0.0; }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -338,15 +341,17 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvArgs& a, f32x16 (&a
                 }
                 if (mok[i]) {
                     *reinterpret_cast<float4*>(a.y + opix[i] * a.Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
+                    if (a.stat_part) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { s1[4 * gq + e] += v[e]; s2[4 * gq + e] += v[e] * v[e]; }
+                        for (int e = 0; e < 4; ++e) { const double d = (double)v[e]; s1[4 * gq + e] += d; s2[4 * gq + e] += d * d; }
+                    }
                 }
             }
         if (a.stat_part) {
             // per-channel sums of this workgroup's tile: 32 pixel lanes -> waves (WM) -> one store per channel
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const double d1 = half32_sum_hi((double)s1[e]), d2 = half32_sum_hi((double)s2[e]);
+                const double d1 = half32_sum_hi(s1[e]), d2 = half32_sum_hi(s2[e]);
                 if (l31 == 31) {
                     const int c = wn * (BN / WN) + 32 * j + 8 * (e >> 2) + 4 * khalf + (e & 3);
                     red[(wm * BN + c) * 2 + 0] = d1;
@@ -1628,7 +1633,7 @@ int block_pixels_v2(int cout, long M) {
 
 int block_pixels_v1(int cout, long M) {
     if (cout >= 64) return M >= 32768 ? 128 : 64;
-    return cout == 32 ? 128 : 256;
+    return cout >= 32 ? 128 : 256;                         // launch_conv: 128 x 32 tiles for 32 and 48 channels, 256 x 16 for 16
 }
 
 // Third-generation kernel (bf16x3 arithmetic, option conv_arith = 1): Cin % 64 == 0 (an even number of K-steps), Cout % 64 == 0.

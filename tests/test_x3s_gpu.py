@@ -652,6 +652,51 @@ def test_x3s_two_workgroups_per_cu_configuration(case):
     assert rel_err(out[105][0], yo) < 1e-5
 
 
+@pytest.mark.parametrize("cfg,bm", [(102, 128), (104, 256)])
+@pytest.mark.parametrize("case", [(6, 64, 14, 14, 128), (37, 64, 14, 14, 64), (5, 128, 7, 7, 64), (42, 64, 14, 14, 512)])
+def test_x3s_configurations_one_and_three_by_option(case, cfg, bm):
+    """Tile configurations 1 (128 pixels, 4 waves, a patch of <= 320 pixels: x3s_choose takes it where 256-pixel tiles give fewer
+    than 160 workgroups and 128-pixel tiles at least 160, which no shape of X3S_CASES does) and 3 (256 pixels, 4 waves of 64 x 64,
+    by option only), forced through conv_cfg = 102 / 104 at the shapes of the test above: forward, statistics partials and data
+    gradient against fp64 at 1e-5, the row count of the partials = the configuration's tile count, and forward and data gradient
+    bitwise equal to the 8-wave configuration (conv_cfg = 106) -- every output element sums the same products in the same
+    order, whichever wave owns it."""
+    n, cin, h, w, cout = case
+    L, lib = dmcnet_amd._lib, dmcnet_amd._lib.load()
+    x, wt, go = rnd(311, (n, cin, h, w)), rnd(312, (cout, cin, 3, 3)) * 0.1, rnd(313, (n, cout, h, w))
+    xo = x.double().requires_grad_(True)
+    yo = F.conv2d(xo, wt.double(), None, 1, 1)
+    (yo * go.double()).sum().backward()
+    yo = yo.detach()
+    xs = ops.x3s_split(x.to(DEV).contiguous(memory_format=CL))
+    dys = ops.x3s_split(go.to(DEV).contiguous(memory_format=CL))
+    wf, wtr = ops.x3s_pack_weights(wt.to(DEV).contiguous(memory_format=CL))
+    before = lib.dmc_get_option(b"conv_cfg")
+    out = {}
+    try:
+        for c in (cfg, 106):
+            L.check(lib.dmc_set_option(b"conv_cfg", c), "dmc_set_option")
+            blocks = lib.dmc_x3s_conv_stat_blocks(n, h, w, cout)
+            y, part = ops.x3s_conv_fwd(xs, wf, n, h, w, cin, cout, want_stats=True)
+            dx = ops.x3s_conv_dgrad(dys, wtr, n, h, w, cin, cout)
+            out[c] = (y, dx, part, blocks)
+    finally:
+        L.check(lib.dmc_set_option(b"conv_cfg", before), "dmc_set_option")
+    y, dx, part, blocks = out[cfg]
+    assert blocks == (n * h * w + bm - 1) // bm and part.shape[0] == blocks          # the forced configuration is the one that ran
+    assert rel_err(y, yo) < 1e-5
+    assert rel_err(dx, xo.grad) < 1e-5
+    s = part.sum(0).cpu()
+    yd = y.double().permute(1, 0, 2, 3).reshape(cout, -1).cpu()
+    assert float((s[:, 0] - yd.sum(1)).abs().max()) <= 1e-9 * float(yd.abs().sum(1).max())
+    assert float((s[:, 1] - (yd * yd).sum(1)).abs().max()) <= 1e-9 * float((yd * yd).sum(1).max())
+    yr = yo.permute(1, 0, 2, 3).reshape(cout, -1)
+    assert float((s[:, 0] - yr.sum(1)).abs().max()) <= 1e-5 * float(yr.abs().sum(1).max())
+    assert float((s[:, 1] - (yr * yr).sum(1)).abs().max()) <= 1e-5 * float((yr * yr).sum(1).max())
+    assert torch.equal(y, out[106][0]) and torch.equal(dx, out[106][1])
+    assert float((part.sum(0) - out[106][2].sum(0)).abs().max()) <= 1e-12 * float(out[106][2].sum(0).abs().max())
+
+
 def test_statistics_partials_sized_under_another_option_are_refused():
     """dmc_x3s_conv_stat_blocks / dmc_conv_nhwc_stat_blocks and the forward each read the tile-configuration option: a
     buffer sized before an option change must be REFUSED by the launch (it would be overrun), not written."""
