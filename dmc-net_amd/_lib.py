@@ -210,6 +210,20 @@ SIGNATURES = {
     "dmc_densetrain_layer_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
     "dmc_densetrain_layer_dgrad": (_I, [_P] * 2 + [_I] * 8 + [_P]),
     "dmc_densetrain_export": (_I, [_P] * 2 + [_I] * 4 + [_P]),
+    "dmc_ef_supported": (_I, [_I] * 6),
+    "dmc_ef_head_wgrad_workspace_bytes": (_Z, [_I] * 4),
+    "dmc_ef_layer_wgrad_workspace_bytes": (_Z, [_I] * 5),
+    "dmc_ef_layer_mask_workspace_bytes": (_Z, [_I] * 4),
+    "dmc_ef_first_bwd_workspace_bytes": (_Z, [_I] * 3),
+    "dmc_ef_first": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "dmc_ef_layer": (_I, [_P] * 3 + [_I] * 6 + [_P]),
+    "dmc_ef_head": (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    "dmc_ef_head_dgrad": (_I, [_P] * 3 + [_I] * 5 + [_P]),
+    "dmc_ef_head_wgrad": (_I, [_P] * 5 + [_I] * 5 + [_P]),
+    "dmc_ef_layer_mask": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "dmc_ef_layer_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "dmc_ef_layer_dgrad": (_I, [_P] * 2 + [_I] * 6 + [_P]),
+    "dmc_ef_first_bwd": (_I, [_P] * 9 + [_I] * 5 + [_P]),
 }
 
 _lib = None

@@ -20,6 +20,9 @@ the five middle units, forward and backward, on csrc/ctx_bn.hip (``ops.bn_leaky`
 ``DMC_CTX_TRAIN_ENDS=1`` (``CTX_TRAIN_ENDS``, off by default, effective only with ``CTX_TRAIN``) moves the two ends onto
 csrc/ctx_ends.hip as well: the first unit's 5 -> 32 convolution (``ops.ctx_first_conv``), the heads' 32 -> 2 convolutions
 (``ops.ctx_head_convs``) and, together with ``CTX_TRAIN_BN``, the heads' BatchNorm + LeakyReLU (``ops.bn_leaky_planes``).
+EstimatorDenseNetTinyEarlyFusionSum / Stack have kernels of their own as well (csrc/early_fusion.hip: ``ops.early_fusion_eval`` with
+``DMC_EF_EVAL=1``, ``ops.early_fusion_train`` with ``DMC_EF_TRAIN=1``); both routes measured slower than the stock modules and are
+off by default.
 Passing ``arch_d`` selects the GAN variant.
 """
 import os as _os
@@ -47,6 +50,18 @@ DENSE_EVAL_ALL = _os.environ.get("DMC_DENSE_EVAL", "") == "1"
 #: function on the feature buffer of the eval route -- forward csrc/dense_eval.hip, backward csrc/dense_train.hip (``ops.dense_train``)
 #: -- where ``ops.dense_train_supported`` accepts the network and the input; otherwise, and by default, the stock loop.
 DENSE_TRAIN = _os.environ.get("DMC_DENSE_TRAIN", "0") == "1"
+#: EstimatorDenseNetTinyEarlyFusionSum / Stack under no_grad run on the kernels of csrc/early_fusion.hip (ops.early_fusion_eval: one
+#: feature buffer, 1 + 4 + 1 launches per frame range, no concatenation) where ops.early_fusion_supported accepts the network and
+#: the input and the class is on the route: DMC_EF_EVAL=0 (read once, here) always the stock modules, bit for bit; DMC_EF_EVAL=1
+#: (EF_EVAL_ALL) the route for both classes; unset, a class takes it only if its EF_EVAL_BY_DEFAULT says that it measured faster
+#: than the stock modules in every A/B pair.
+EF_EVAL = _os.environ.get("DMC_EF_EVAL", "1") != "0"
+EF_EVAL_ALL = _os.environ.get("DMC_EF_EVAL", "") == "1"
+#: DMC_EF_TRAIN=1 (read once, here; default 0): with autograd enabled, the two early-fusion estimators run as one autograd function
+#: on the feature buffer, forward and backward on csrc/early_fusion.hip (``ops.early_fusion_train``), where
+#: ``ops.early_fusion_train_supported`` accepts the network and the input (never when the input requires a gradient); otherwise,
+#: and by default, the stock loop.
+EF_TRAIN = _os.environ.get("DMC_EF_TRAIN", "0") == "1"
 #: DMC_CTX_TRAIN=1 (read once, here; default 0): with autograd enabled, the convolutions of the five middle units of ContextNetwork /
 #: ContextNetworkAtt run on the kernels of csrc/dconv.hip (ops.context_train: ops.dilated_conv per unit, then the unit's own
 #: BatchNorm2d and LeakyReLU; the first unit and the heads stay stock) whenever ops.context_train_supported accepts the network
@@ -150,6 +165,13 @@ class EstimatorDenseNetTiny(DenseEstimatorBase):
 
 
 class _EarlyFusion(nn.Module):
+    """EstimatorDenseNetTinyEarlyFusionSum / Stack (code/dmcnet/model.py:197-250).  ``forward`` dispatches like
+    DenseEstimatorBase.forward: with autograd off ops.early_fusion_eval (see EF_EVAL / EF_EVAL_ALL / EF_EVAL_BY_DEFAULT), with
+    autograd on and EF_TRAIN ops.early_fusion_train, otherwise the stock loop."""
+
+    #: True on a class whose eval route measured faster than the stock modules in every A/B pair (profiles/early_fusion_bench.json)
+    EF_EVAL_BY_DEFAULT = False
+
     def __init__(self, stack):
         super().__init__()
         self.conv_0_mv, self.conv_0_r = _unit(2, 8), _unit(3, 8)
@@ -161,6 +183,10 @@ class _EarlyFusion(nn.Module):
         self.stack = stack
 
     def forward(self, x):
+        if EF_EVAL and (EF_EVAL_ALL or self.EF_EVAL_BY_DEFAULT) and ops.early_fusion_supported(self, x):
+            return ops.early_fusion_eval(self, x)
+        if EF_TRAIN and ops.early_fusion_train_supported(self, x):
+            return ops.early_fusion_train(self, x)
         m, r = self.conv_0_mv(x[:, :2]), self.conv_0_r(x[:, 2:])
         x = torch.cat((m, r), 1) if self.stack else m + r
         for i in (1, 2, 3, 4):

@@ -3074,6 +3074,272 @@ def dense_train(net, x):
     return _DenseTrain.apply(x, (lay, widths), *params)
 
 
+# ---- EstimatorDenseNetTinyEarlyFusionSum / Stack: eval and training on one feature buffer (csrc/early_fusion.hip) ----
+
+_EF_WIDTHS = (8, 6, 4, 2)      # conv_1 .. conv_4
+_EF_SLOPE = 0.1
+
+
+def early_fusion_layout(stack):
+    """The feature buffer of an early-fusion estimator (``stack``: cat(m, r), else m + r), as a dict:
+      "offsets"  slot name -> (first buffer channel, live channels), in production order: "m" and "r" (Stack) or "s" (Sum), then
+                 "y1" .. "y4"; every slot is padded to a multiple of 4 channels;
+      "ct"       channels per pixel of the buffer (Stack 40, Sum 32);
+      "layers"   per conv_k, k = 1 .. 4: (K, R, index) -- it reads buffer channels [0, K) and writes [K, K + round_up4(R)); ``index``
+                 (int64 [K]) maps a buffer channel to the input channel of the reference's conv_k, whose input is
+                 cat(y_{k-1}, ..., y_1, base) with base = cat(m, r) or s, or -1 for a pad;
+      "head"     (K, 2, index) of predict_flow the same way, K = ct.
+    A pure function of its argument."""
+    stack = bool(stack)
+    base = 16 if stack else 8
+    offsets = {"m": (0, 8), "r": (8, 8)} if stack else {"s": (0, 8)}
+    first = [base]
+    for v in _EF_WIDTHS:
+        first.append(first[-1] + (v + 3) // 4 * 4)
+    for j, v in enumerate(_EF_WIDTHS):
+        offsets["y%d" % (j + 1)] = (first[j], v)
+
+    def index(k):                                                  # the input of conv_k (k == 5: predict_flow): y_1 .. y_{k-1} exist
+        idx = torch.full((first[k - 1],), -1, dtype=torch.int64)
+        ref = sum(_EF_WIDTHS[:k - 1])                              # the base comes last in the reference's order ...
+        idx[0:base] = torch.arange(ref, ref + base)
+        for j in range(k - 1):                                     # ... behind y_1, which is behind y_2, ...
+            ref -= _EF_WIDTHS[j]
+            idx[first[j]:first[j] + _EF_WIDTHS[j]] = torch.arange(ref, ref + _EF_WIDTHS[j])
+        return idx
+
+    layers = [(first[k - 1], _EF_WIDTHS[k - 1], index(k)) for k in (1, 2, 3, 4)]
+    return {"offsets": offsets, "ct": first[-1], "layers": layers, "head": (first[-1], 2, index(5))}
+
+
+def _ef_plan(net, on_device=True):
+    """(stack, conv_0_mv, conv_0_r, [conv_1 .. conv_4], predict_flow) of a model._EarlyFusion with the stock forward whose every unit
+    the kernels serve, or None.  ``on_device=False`` leaves out the test that the parameters are CUDA tensors."""
+    base = next((c for c in type(net).__mro__ if c.__name__ == "_EarlyFusion"), None)
+    if base is None or type(net).forward is not base.forward or not isinstance(getattr(net, "stack", None), bool):
+        return None
+
+    def unit(name, cin, cout):
+        u = getattr(net, name, None)
+        if not isinstance(u, torch.nn.Sequential) or len(u) != 2 or not isinstance(u[1], torch.nn.LeakyReLU):
+            return None
+        if abs(u[1].negative_slope - _EF_SLOPE) > 1e-12 or not _dense_conv_ok(u[0], cin, cout, on_device):
+            return None
+        return u[0]
+
+    mv, res = unit("conv_0_mv", 2, 8), unit("conv_0_r", 3, 8)
+    if mv is None or res is None:
+        return None
+    convs, c = [], 16 if net.stack else 8
+    for i, v in enumerate(_EF_WIDTHS):
+        conv = unit("conv_%d" % (i + 1), c, v)
+        if conv is None:
+            return None
+        convs.append(conv)
+        c += v
+    head = getattr(net, "predict_flow", None)
+    if not _dense_conv_ok(head, c, 2, on_device):
+        return None
+    return net.stack, mv, res, convs, head
+
+
+def _ef_input_ok(x):
+    return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 5 and x.numel() > 0
+
+
+def _ef_ranges_ok(lay, chunks, h, w):
+    lib = _lib.load()
+    sizes = sorted({b - a for a, b in chunks})
+    return all(lib.dmc_ef_supported(f, h, w, lay["ct"], k, r) for f in sizes for k, r, _ in lay["layers"] + [lay["head"]])
+
+
+def early_fusion_supported(net, x):
+    """True if ``net`` (model.EstimatorDenseNetTinyEarlyFusionSum / Stack: a model._EarlyFusion with the stock forward) can be
+    evaluated on ``x`` by the kernels of csrc/early_fusion.hip: no autograd, a non-empty CUDA fp32 [N, 5, H, W] input, every unit a
+    Sequential(Conv2d 3x3 / stride 1 / padding 1 with bias, LeakyReLU(0.1)) of _EarlyFusion's channel counts, predict_flow a Conv2d
+    of the same geometry with 2 channels, CUDA fp32 parameters, a frame range that fits (dense_eval_chunks) and every layer
+    accepted by dmc_ef_supported."""
+    if torch.is_grad_enabled() or not _ef_input_ok(x):
+        return False
+    plan = _ef_plan(net)
+    if plan is None:
+        return False
+    lay = early_fusion_layout(plan[0])
+    n, _, h, w = x.shape
+    try:
+        chunks = dense_eval_chunks(n, h, w, lay["ct"])
+    except ValueError:
+        return False
+    return _ef_ranges_ok(lay, chunks, h, w)
+
+
+def _ef_weights(lay, convs, head):
+    """[(w [R][9][K] in buffer order, bias [R], K, R), ...] of conv_1 .. conv_4 and of predict_flow; ``convs`` / ``head`` are modules or
+    _ConvView pairs."""
+    out = []
+    for conv, (k, r, index) in zip(list(convs) + [head], lay["layers"] + [lay["head"]]):
+        wp, bp = _dense_weight(conv, k, r, index)
+        out.append((wp, bp, k, r))
+    return out
+
+
+def _ef_forward(lib, stack, lay, x, first, weights, chunks, keep):
+    """The forward launches per frame range: dmc_ef_first, four dmc_ef_layer, dmc_ef_head.  ``first`` = (w_mv, b_mv, w_r, b_r).  With
+    ``keep`` every range's (a, b, feat, signs) is returned as well (signs: the sign plane, Sum only)."""
+    ct = lay["ct"]
+    n, _, h, w = x.shape
+    dev = x.device
+    s = _stream()
+    out = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+    kept = []
+    for a, b in chunks:
+        f = b - a
+        feat = torch.empty((f, h, w, ct), dtype=torch.float32, device=dev)
+        signs = torch.empty((f, h, w), dtype=torch.int16, device=dev) if keep and not stack else None
+        _lib.check(lib.dmc_ef_first(_lib.ptr(x[a:b]), _lib.ptr(first[0]), _lib.ptr(first[1]), _lib.ptr(first[2]), _lib.ptr(first[3]),
+                                    _lib.ptr(feat), _lib.ptr(signs), f, h, w, ct, int(stack), s), "dmc_ef_first")
+        for wp, bp, k, r in weights[:-1]:
+            _lib.check(lib.dmc_ef_layer(_lib.ptr(feat), _lib.ptr(wp), _lib.ptr(bp), f, h, w, ct, k, r, s), "dmc_ef_layer")
+        hw_, hb, hk, _ = weights[-1]
+        _lib.check(lib.dmc_ef_head(_lib.ptr(feat), _lib.ptr(hw_), _lib.ptr(hb), _lib.ptr(out[a:b]), f, h, w, ct, hk, s), "dmc_ef_head")
+        if keep:
+            kept.append((a, b, feat, signs))
+        del feat
+    return out, kept
+
+
+def early_fusion_eval(net, x):
+    """``net(x)`` of an EstimatorDenseNetTinyEarlyFusionSum / Stack (-> gen_flow [N, 2, H, W]) with autograd off on the kernels of
+    csrc/early_fusion.hip: per frame range (dense_eval_chunks) one NHWC fp32 feature buffer, dmc_ef_first, one dmc_ef_layer per
+    conv_1 .. conv_4 that reads a prefix of the buffer and appends its slot, and dmc_ef_head -- no concatenation.  The weights are
+    permuted into buffer order once per call.  Requires early_fusion_supported(net, x)."""
+    lib = _lib.load()
+    if not early_fusion_supported(net, x):
+        raise _lib.DmcHipError("early_fusion_eval: the network or the input is not served by the kernels (early_fusion_supported)")
+    stack, mv, res, convs, head = _ef_plan(net)
+    lay = early_fusion_layout(stack)
+    x = x.contiguous()
+    n, _, h, w = x.shape
+    with _span("early_fusion_eval"):
+        first = [t.detach().contiguous() for t in (mv.weight, mv.bias, res.weight, res.bias)]
+        out, _ = _ef_forward(lib, stack, lay, x, first, _ef_weights(lay, convs, head), dense_eval_chunks(n, h, w, lay["ct"]), False)
+    return out
+
+
+def early_fusion_train_supported(net, x):
+    """True if ``net(x)`` of an early-fusion estimator can run WITH autograd on the kernels of csrc/early_fusion.hip, forward and
+    backward: autograd enabled, a non-empty CUDA fp32 [N, 5, H, W] input that does NOT require a gradient (no input gradient is
+    built: such a call takes the stock modules), the structure early_fusion_supported asks for, frame ranges that fit
+    (dense_eval_chunks under DENSE_TRAIN_BUDGET) and every range and layer accepted by dmc_ef_supported."""
+    if not torch.is_grad_enabled() or not _ef_input_ok(x) or x.requires_grad:
+        return False
+    plan = _ef_plan(net)
+    if plan is None:
+        return False
+    lay = early_fusion_layout(plan[0])
+    n, _, h, w = x.shape
+    try:
+        chunks = _dense_train_chunks(n, h, w, lay["ct"])
+    except ValueError:
+        return False
+    return _ef_ranges_ok(lay, chunks, h, w)
+
+
+class _EarlyFusionTrain(torch.autograd.Function):
+    """An early-fusion estimator over ``x`` and its fourteen parameters (w_mv, b_mv, w_r, b_r, w_1, b_1, ..., w_4, b_4, w_head,
+    b_head).  Forward: the launches of early_fusion_eval per frame range; every range's feature buffer and, for Sum, sign plane is
+    kept.  Backward: per range one gradient buffer of the same layout, from the head down; the ranges' parameter gradients are
+    added in range order.  No gradient with respect to ``x``."""
+
+    @staticmethod
+    def forward(ctx, x, meta, *params):
+        lib = _lib.load()
+        stack, lay = meta
+        x = x.contiguous()
+        n, _, h, w = x.shape
+        with _span("early_fusion_train_fwd"):
+            first = [p.detach().contiguous() for p in params[:4]]
+            views = [_ConvView(params[4 + 2 * i], params[5 + 2 * i]) for i in range(5)]
+            weights = _ef_weights(lay, views[:4], views[4])
+            out, kept = _ef_forward(lib, stack, lay, x, first, weights, _dense_train_chunks(n, h, w, lay["ct"]), True)
+        ctx.save_for_backward(x)
+        ctx.ef = (stack, lay, kept, weights)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        lib = _lib.load()
+        stack, lay, kept, weights = ctx.ef
+        x, = ctx.saved_tensors
+        ct = lay["ct"]
+        n, _, h, w = x.shape
+        dout = dout.contiguous()
+        dev = dout.device
+        s = _stream()
+
+        def work(nbytes):
+            return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+        with _span("early_fusion_train_bwd"):
+            total = None
+            hw_, _, hk, _ = weights[-1]
+            for a, b, feat, signs in kept:
+                f = b - a
+                G = torch.empty((f, h, w, ct), dtype=torch.float32, device=dev)
+                dws = [torch.empty((r, 3, 3, k), dtype=torch.float32, device=dev) for _, _, k, r in weights]
+                dbs = [torch.empty((r,), dtype=torch.float32, device=dev) for _, _, _, r in weights]
+                firsts = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((8, 2, 3, 3), (8,), (8, 3, 3, 3), (8,))]
+                dpart = dout[a:b]
+                _lib.check(lib.dmc_ef_head_dgrad(_lib.ptr(dpart), _lib.ptr(hw_), _lib.ptr(G), f, h, w, ct, hk, s), "dmc_ef_head_dgrad")
+                ws = work(lib.dmc_ef_head_wgrad_workspace_bytes(f, h, w, hk))
+                _lib.check(lib.dmc_ef_head_wgrad(_lib.ptr(dpart), _lib.ptr(feat), _lib.ptr(dws[4]), _lib.ptr(dbs[4]), _lib.ptr(ws), f, h, w, ct, hk, s),
+                           "dmc_ef_head_wgrad")
+                for i in (3, 2, 1, 0):
+                    wp, _, k, r = weights[i]
+                    ws = work(lib.dmc_ef_layer_mask_workspace_bytes(f, h, w, r))
+                    _lib.check(lib.dmc_ef_layer_mask(_lib.ptr(feat), _lib.ptr(G), _lib.ptr(dbs[i]), _lib.ptr(ws), f, h, w, ct, k, r, s),
+                               "dmc_ef_layer_mask")
+                    ws = work(lib.dmc_ef_layer_wgrad_workspace_bytes(f, h, w, k, r))
+                    _lib.check(lib.dmc_ef_layer_wgrad(_lib.ptr(feat), _lib.ptr(G), _lib.ptr(dws[i]), _lib.ptr(ws), f, h, w, ct, k, r, s),
+                               "dmc_ef_layer_wgrad")
+                    _lib.check(lib.dmc_ef_layer_dgrad(_lib.ptr(G), _lib.ptr(wp), f, h, w, ct, k, r, s), "dmc_ef_layer_dgrad")
+                ws = work(lib.dmc_ef_first_bwd_workspace_bytes(f, h, w))
+                _lib.check(lib.dmc_ef_first_bwd(_lib.ptr(G), _lib.ptr(x[a:b]), _lib.ptr(signs), _lib.ptr(feat), _lib.ptr(firsts[0]),
+                                                _lib.ptr(firsts[1]), _lib.ptr(firsts[2]), _lib.ptr(firsts[3]), _lib.ptr(ws), f, h, w, ct,
+                                                int(stack), s), "dmc_ef_first_bwd")
+                del G, ws
+                part = firsts + dws + dbs
+                if total is None:
+                    total = part
+                else:                                              # the ranges in order
+                    for t, p in zip(total, part):
+                        t.add_(p)
+            ctx.ef = None
+            grads = list(total[:4])
+            dws, dbs = total[4:9], total[9:14]
+            for i, (_, r, index) in enumerate(lay["layers"] + [lay["head"]]):
+                grads.append(_dense_weight_grad(dws[i], r, index))
+                grads.append(dbs[i])
+        return (None, None) + tuple(g if ctx.needs_input_grad[2 + j] else None for j, g in enumerate(grads))
+
+
+def early_fusion_train(net, x):
+    """``net(x)`` of an EstimatorDenseNetTinyEarlyFusionSum / Stack (-> gen_flow [N, 2, H, W]) with autograd, as ONE
+    torch.autograd.Function over ``x`` and the fourteen parameters: the forward is early_fusion_eval's launches per frame range with
+    every range's feature buffer (and, for Sum, the sign plane of the two first convolutions) kept; the backward runs in a second
+    buffer of the same layout -- head, then per layer the LeakyReLU mask with the bias gradient, the weight gradient and the in-place
+    data gradient, then the two first convolutions' gradients -- without a concatenation or an atomic.  The weight gradients come back
+    in the parameters' own layout; ``x`` gets no gradient.  Raises DmcHipError unless early_fusion_train_supported(net, x)."""
+    if not early_fusion_train_supported(net, x):
+        raise _lib.DmcHipError("early_fusion_train: the network or the input is not served by the kernels (early_fusion_train_supported)")
+    stack, mv, res, convs, head = _ef_plan(net)
+    params = [mv.weight, mv.bias, res.weight, res.bias]
+    for c in convs + [head]:
+        params += [c.weight, c.bias]
+    return _EarlyFusionTrain.apply(x, (stack, early_fusion_layout(stack)), *params)
+
+
 # ---- ContextNetwork / ContextNetworkAtt in training: the dilated convolutions of the middle units (csrc/dconv.hip) ----
 
 def _dconv_geom_ok(x, cin, cout, dilation):

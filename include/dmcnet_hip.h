@@ -1039,6 +1039,72 @@ int dmc_densetrain_layer_dgrad(float* G, const void* wpack_t, int N, int H, int 
                                dmc_stream_t stream);
 int dmc_densetrain_export(const float* G, float* dx_nchw, int N, int H, int W, int CT, dmc_stream_t stream);
 
+/* ---- EstimatorDenseNetTinyEarlyFusionSum / EstimatorDenseNetTinyEarlyFusionStack, forward and backward (csrc/early_fusion.hip) ----
+ * Replaces: the two early-fusion estimators of code/dmcnet/model.py:197-250 -- m = LeakyReLU_0.1(conv_0_mv(x[:, :2])),
+ *           r = LeakyReLU_0.1(conv_0_r(x[:, 2:])), x = cat(m, r) (Stack) or m + r (Sum), x = cat(LeakyReLU_0.1(conv_i(x)), x) for
+ *           i = 1 .. 4, predict_flow(x); every convolution 3x3 / stride 1 / padding 1 with bias -- and autograd's backward of it
+ *           with respect to the fourteen parameters, without materialising a concatenation.
+ * The feature buffer: feat NHWC fp32 [N][H][W][CT], channels in slots in production order, every slot padded with +0.0 to a
+ *   multiple of 4 channels.  Sum: s (0, 8), y1 (8, 8), y2 (16, 6), y3 (24, 4), y4 (28, 2), CT 32.  Stack: m (0, 8), r (8, 8),
+ *   y1 (16, 8), y2 (24, 6), y3 (32, 4), y4 (36, 2), CT 40 (first channel, live channels; ops.early_fusion_layout).  A layer reads
+ *   the prefix [0, K) of every pixel and writes [K, K + round_up4(R)) of the same buffer; the caller permutes each weight's input
+ *   channels into buffer order with zero columns for the pad channels: w [R][9][K] = [output channel][tap ky * 3 + kx][buffer
+ *   channel].  G [N][H][W][CT] fp32, same layout, holds dL/d(feat).  o(t) = the pixel offset (ky - 1, kx - 1) of tap t; a tap
+ *   outside the frame contributes nothing.
+ * dmc_ef_supported: 1 when N, H, W > 0, CT > 0, CT % 4 == 0, CT <= 64, K > 0, K % 4 == 0, R in {2, 4, 6, 8}, N * H * W * CT < 2^31
+ *   (what one launch indexes; the caller splits larger batches into frame ranges) and either K + round_up4(R) <= CT (a layer) or
+ *   R == 2 with K <= CT (the head); else 0.  The layer entry points (dmc_ef_layer, dmc_ef_layer_mask, dmc_ef_layer_wgrad,
+ *   dmc_ef_layer_dgrad) also need K + round_up4(R) <= CT when R == 2.
+ * dmc_ef_*_workspace_bytes: the bytes the entry point of that name uses of `workspace` (partial sums per run of 1024 pixels);
+ *   0 for an unsupported shape.  parts = ceil(N H W / 1024).  head_wgrad: parts * (18 K + 2) * 4.  layer_wgrad: parts * R * 9 * K * 4.
+ *   layer_mask: parts * round_up4(R) * 4.  first_bwd: parts * 376 * 4.
+ * dmc_ef_first: x NCHW [N][5][H][W], w_mv [8][2][3][3], b_mv [8], w_r [8][3][3][3], b_r [8] (PyTorch's native layouts).  a =
+ *   conv_0_mv(x[:, :2]) + b_mv, b = conv_0_r(x[:, 2:]) + b_r, each summed in its own fixed order (the same bits for both values of
+ *   `stack`).  stack = 1: feat[.][0, 8) = leaky(a), feat[.][8, 16) = leaky(b), CT >= 16.  stack = 0: feat[.][0, 8) = leaky(a) +
+ *   leaky(b), CT >= 8.  signs (uint16 [N H W], optional: written only when non-NULL): bit c = (a_c > 0), bit 8 + c = (b_c > 0).
+ *   Every other channel of feat is left as it is.
+ * dmc_ef_layer: feat[.][K, K + R) = leaky_0.1(conv3x3(feat[.][0, K)) + bias[R]) in place, feat[.][K + R, K + round_up4(R)) = +0.0.
+ *   Reads only channels < K, writes only its slot.
+ * dmc_ef_head: out NCHW [N][2][H][W] = conv3x3(feat[.][0, K)) + bias[2], w [2][9][K]; feat is read only.
+ * dmc_ef_head_dgrad: G[m][c] = sum_t sum_co dout[m - o(t)][co] w[co][t][c] for c < K and 0 for K <= c < CT (dout NCHW
+ *   [N][2][H][W]): writes EVERY float of G.
+ * dmc_ef_head_wgrad: dw [2][9][K] = sum_m dout[m][co] feat[m + o(t)][c], db [2] = sum_m dout[m][co].
+ * dmc_ef_layer_mask: G[.][K + r] <- feat[.][K + r] > 0 ? g : 0.1f * g in place for r < round_up4(R), db [R] = the sums of the
+ *   result over the pixels.  Every other channel of G is left as it is; feat is read only.
+ * dmc_ef_layer_wgrad: dw [R][9][K] = sum_m G[m][K + r] feat[m + o(t)][c].  Reads feat channels [0, K) and G channels
+ *   [K, K + round_up4(R)) only.
+ * dmc_ef_layer_dgrad: G[m][c] += sum_t sum_r G[m - o(t)][K + r] w[r][t][c] in place for c < K.  Reads channels
+ *   [K, K + round_up4(R)) (the gathered slot), reads and writes channels < K of the lane's own pixel: disjoint byte sets.
+ * dmc_ef_first_bwd: from G's base slot, x and the branch of each LeakyReLU -- stack = 0: both from `signs` (feat may be NULL),
+ *   ga_c = G[.][c] * (bit c ? 1 : 0.1f), gb_c = G[.][c] * (bit 8 + c ? 1 : 0.1f); stack = 1: from the stored activations (signs may
+ *   be NULL), ga_c = G[.][c] * (feat[.][c] > 0 ? 1 : 0.1f), gb_c = G[.][8 + c] * (feat[.][8 + c] > 0 ? 1 : 0.1f) -- dw_mv [8][2][3][3] =
+ *   sum_m ga_c[m] x[m + o(t)][i], db_mv [8] = sum_m ga_c[m], dw_r [8][3][3][3] and db_r [8] the same of gb and x[:, 2:].  No gradient
+ *   with respect to x is produced.
+ * Every sum over pixels is formed as fp32 fmaf runs of at most 1024 pixels in order; the runs' partial sums are added in run
+ *   order.  Plain fp32 FMAs in a fixed order throughout: deterministic, no atomics, a forward result independent of the batch
+ *   its frame is in; the caller owns every buffer; nothing allocates or synchronises; inputs are read only.
+ * DMC_E_INVALID before any launch (nothing written): a NULL required pointer, an unsupported shape. */
+int dmc_ef_supported(int N, int H, int W, int CT, int K, int R);
+size_t dmc_ef_head_wgrad_workspace_bytes(int N, int H, int W, int K);
+size_t dmc_ef_layer_wgrad_workspace_bytes(int N, int H, int W, int K, int R);
+size_t dmc_ef_layer_mask_workspace_bytes(int N, int H, int W, int R);
+size_t dmc_ef_first_bwd_workspace_bytes(int N, int H, int W);
+int dmc_ef_first(const float* x_nchw, const float* w_mv, const float* b_mv, const float* w_r, const float* b_r, float* feat,
+                 unsigned short* signs, int N, int H, int W, int CT, int stack, dmc_stream_t stream);
+int dmc_ef_layer(float* feat, const float* w, const float* bias, int N, int H, int W, int CT, int K, int R, dmc_stream_t stream);
+int dmc_ef_head(const float* feat, const float* w, const float* bias, float* out_nchw, int N, int H, int W, int CT, int K,
+                dmc_stream_t stream);
+int dmc_ef_head_dgrad(const float* dout_nchw, const float* w, float* G, int N, int H, int W, int CT, int K, dmc_stream_t stream);
+int dmc_ef_head_wgrad(const float* dout_nchw, const float* feat, float* dw, float* db, void* workspace, int N, int H, int W, int CT,
+                      int K, dmc_stream_t stream);
+int dmc_ef_layer_mask(const float* feat, float* G, float* db, void* workspace, int N, int H, int W, int CT, int K, int R,
+                      dmc_stream_t stream);
+int dmc_ef_layer_wgrad(const float* feat, const float* G, float* dw, void* workspace, int N, int H, int W, int CT, int K, int R,
+                       dmc_stream_t stream);
+int dmc_ef_layer_dgrad(float* G, const float* w, int N, int H, int W, int CT, int K, int R, dmc_stream_t stream);
+int dmc_ef_first_bwd(const float* G, const float* x_nchw, const unsigned short* signs, const float* feat, float* dw_mv, float* db_mv,
+                     float* dw_r, float* db_r, void* workspace, int N, int H, int W, int CT, int stack, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
