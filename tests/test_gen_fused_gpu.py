@@ -28,10 +28,13 @@ def test_fused_forward_is_the_default():
 
 
 # widths: <= 62 one pixel half; 63 .. 118 two halves of one strip; 119 .. 224 two strips (odd widths: unequal strips);
-# heights below the 11-step pipeline depth; 225 takes the layer-by-layer kernels
+# heights below the 11-step pipeline depth; 225 takes the layer-by-layer kernels; the last three: few frames in flight, so a strip is
+# cut into row bands (gen_fused_inl.h: vsplit) that do not divide H evenly -- 25 + 24 rows, three bands on two strips, four bands
+# with a shorter last one
 @pytest.mark.parametrize("shape", [(1, 5, 1, 1), (2, 5, 2, 3), (1, 5, 5, 62), (1, 5, 7, 63), (2, 5, 9, 64), (1, 5, 12, 117),
                                    (1, 5, 13, 118), (1, 5, 11, 119), (2, 5, 10, 120), (1, 5, 8, 121), (1, 5, 17, 223),
-                                   (2, 5, 30, 224), (1, 5, 3, 224), (1, 5, 1, 224), (1, 5, 26, 180), (1, 5, 6, 225)])
+                                   (2, 5, 30, 224), (1, 5, 3, 224), (1, 5, 1, 224), (1, 5, 26, 180), (1, 5, 6, 225),
+                                   (1, 5, 49, 64), (1, 5, 74, 120), (2, 5, 99, 36)])
 @pytest.mark.parametrize("delta,fused", [(False, 1), (True, 1)])
 def test_fused_forward_edge_shapes(shape, delta, fused, request):
     before = _set(b"gen_fused", fused)
