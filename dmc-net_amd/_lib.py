@@ -224,6 +224,16 @@ SIGNATURES = {
     "dmc_ef_layer_wgrad": (_I, [_P] * 4 + [_I] * 6 + [_P]),
     "dmc_ef_layer_dgrad": (_I, [_P] * 2 + [_I] * 6 + [_P]),
     "dmc_ef_first_bwd": (_I, [_P] * 9 + [_I] * 5 + [_P]),
+    "dmc_disc_c8_supported": (_I, [_I] * 3),
+    "dmc_disc_c8_stat_blocks": (_I, [_I] * 3),
+    "dmc_disc_c8_fwd": (_I, [_P] * 6 + [_I] * 5 + [_P]),
+    "dmc_disc_c8_dgrad": (_I, [_P] * 3 + [_I] * 3 + [_P]),
+    "dmc_disc_c8_wgrad_bytes": (_Z, [_I] * 3),
+    "dmc_disc_c8_wgrad": (_I, [_P] * 5 + [_I] * 3 + [_P]),
+    "dmc_disc_head_supported": (_I, [_I] * 4),
+    "dmc_disc_head_fwd": (_I, [_P] * 4 + [_I] * 4 + [_P]),
+    "dmc_disc_head_bwd_bytes": (_Z, [_I] * 4),
+    "dmc_disc_head_bwd": (_I, [_P] * 7 + [_I] * 4 + [_P]),
 }
 
 _lib = None

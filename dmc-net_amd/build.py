@@ -7,7 +7,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libdmcnet_hip.so")
-SOURCES = ["gen_tiny.hip", "gen_x3.hip", "gen_fused.hip", "gen_wgrad.hip", "losses.hip", "disc_tail.hip", "bn_act.hip", "prepare.hip", "clip_prep.hip", "stem.hip", "conv_nhwc.hip", "conv_small.hip", "conv_x3s.hip", "conv_x3q.hip", "disc_first.hip", "conv3d_bf16.hip", "pool3d_bf16.hip", "bn3d_bf16.hip", "stem3d_bf16.hip", "unit3d.hip", "coviar_post.hip", "ctx_eval.hip", "dconv.hip", "ctx_bn.hip", "ctx_ends.hip", "dense_eval.hip", "dense_train.hip", "early_fusion.hip"]
+SOURCES = ["gen_tiny.hip", "gen_x3.hip", "gen_fused.hip", "gen_wgrad.hip", "losses.hip", "disc_tail.hip", "bn_act.hip", "prepare.hip", "clip_prep.hip", "stem.hip", "conv_nhwc.hip", "conv_small.hip", "conv_x3s.hip", "conv_x3q.hip", "disc_first.hip", "conv3d_bf16.hip", "pool3d_bf16.hip", "bn3d_bf16.hip", "stem3d_bf16.hip", "unit3d.hip", "coviar_post.hip", "ctx_eval.hip", "dconv.hip", "ctx_bn.hip", "ctx_ends.hip", "dense_eval.hip", "dense_train.hip", "early_fusion.hip", "disc_c8.hip", "disc_head.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function"]

@@ -23,6 +23,9 @@ csrc/ctx_ends.hip as well: the first unit's 5 -> 32 convolution (``ops.ctx_first
 EstimatorDenseNetTinyEarlyFusionSum / Stack have kernels of their own as well (csrc/early_fusion.hip: ``ops.early_fusion_eval`` with
 ``DMC_EF_EVAL=1``, ``ops.early_fusion_train`` with ``DMC_EF_TRAIN=1``); both routes measured slower than the stock modules and are
 off by default.
+The discriminators run end to end on the kernels: Discriminator4's 8 -> 16 block on csrc/disc_c8.hip (``DISC_C8``) and every
+``adv_layer`` on csrc/disc_head.hip (``ops.disc_head``, ``DISC_HEAD``), both on by default; of the two ``nn.Linear``
+heads named above only the classifier's stays a stock op.
 Passing ``arch_d`` selects the GAN variant.
 """
 import os as _os
@@ -77,6 +80,18 @@ CTX_TRAIN_BN = _os.environ.get("DMC_CTX_TRAIN_BN", "0") == "1"
 #: BatchNorm2d + LeakyReLU (+ ReLU) run as ops.bn_leaky_planes.  With all three flags no convolution and no BatchNorm of a
 #: ContextNetwork training step is a stock module.
 CTX_TRAIN_ENDS = _os.environ.get("DMC_CTX_TRAIN_ENDS", "0") == "1"
+#: DMC_DISC_C8 (read once, here): "1" = Discriminator4's 8 -> 16 block runs on csrc/disc_c8.hip (``ops.disc_block`` with ``c8``)
+#: wherever ``ops.disc_block_supported`` accepts it; "0" = F.conv2d + ``ops.disc_tail`` between two layout flips, the stock route,
+#: bit for bit.  Unset = DISC_C8_BY_DEFAULT, which the A/B measurement decides.  ``forward`` reads the attribute
+#: at call time.
+DISC_C8_BY_DEFAULT = True
+DISC_C8 = _os.environ.get("DMC_DISC_C8", "1" if DISC_C8_BY_DEFAULT else "0") == "1"
+#: DMC_DISC_HEAD (read once, here): "1" = every discriminator's ``adv_layer`` on an NHWC activation runs as ``ops.disc_head``
+#: (csrc/disc_head.hip) wherever ``ops.disc_head_supported`` accepts it; "0" = F.linear on a permuted copy of the weight, the stock
+#: route, bit for bit.  Unset = DISC_HEAD_BY_DEFAULT, which the A/B measurement decides.  ``forward`` reads the
+#: attribute at call time.
+DISC_HEAD_BY_DEFAULT = True
+DISC_HEAD = _os.environ.get("DMC_DISC_HEAD", "1" if DISC_HEAD_BY_DEFAULT else "0") == "1"
 
 # ---------------------------------------------------------------------------- generators
 
@@ -310,9 +325,14 @@ class _DiscriminatorBase(nn.Module):
     def forward(self, x):
         """Blocks run on the fused HIP path (``ops.disc_block``: NHWC activations, convolution on the
         fp32 matrix cores with bias / LeakyReLU / mask / BatchNorm statistics in its epilogue) whenever
-        the shape qualifies -- every block of Discriminator..Discriminator3 and Discriminator5 does;
-        otherwise (Discriminator4's 8-channel blocks, CPU tensors) the convolution goes to
-        PyTorch-ROCm and the tail to ``ops.disc_tail``."""
+        the shape qualifies -- every block of Discriminator..Discriminator3 and Discriminator5 does, and
+        Discriminator4's first (2 -> 8, csrc/disc_first.hip) and last (16 -> 32) blocks; its 8 -> 16 block has
+        direct fp32 kernels of its own (csrc/disc_c8.hip) behind ``DISC_C8``.  Otherwise (that block with the
+        switch off, CPU tensors, odd sizes) the convolution goes to PyTorch-ROCm and the tail to ``ops.disc_tail``.
+        ``adv_layer`` on an NHWC activation runs as ``ops.disc_head`` (csrc/disc_head.hip: the weight read in
+        place, no permuted copy) behind ``DISC_HEAD``; with the switch off it is F.linear on a permuted view of
+        the weight.  Both switches are module attributes read here at every call; with both on, no pass of any
+        ``arch_d`` calls a stock convolution or linear op."""
         nhwc = False
         # the Dropout2d keep masks of ALL blocks from one draw (same p everywhere, as the reference's blocks have): 4 launches for the
         # pass instead of 4 per block -- they are ~5 us kernels in front of every block of every discriminator pass
@@ -332,8 +352,8 @@ class _DiscriminatorBase(nn.Module):
             bn = blk[3] if len(blk) == 4 else None
             keep = keeps[name] if keeps is not None else self._keep(name, x, drop)
             first = i == 0 and not nhwc
-            if ops.disc_block_supported(x, conv, first) and (bn is None or not first):
-                x = ops.disc_block(x, conv, keep, bn, self.training, first=first)
+            if ops.disc_block_supported(x, conv, first, c8=DISC_C8) and (bn is None or not first):
+                x = ops.disc_block(x, conv, keep, bn, self.training, first=first, c8=DISC_C8)
                 nhwc = True
                 continue
             x = F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding)
@@ -342,7 +362,10 @@ class _DiscriminatorBase(nn.Module):
         # flatten in the reference's NCHW order (the Linear's weight is laid out for it).  An NHWC (channels_last) activation is
         # NOT copied into that order: the weight's columns are permuted to (h, w, c) instead -- 50 k values against 4.7 M (GAN) /
         # 9.6 M (I3D) per step each way; autograd carries the weight gradient back through the same permutation.
+        # With DISC_HEAD the NHWC activation goes to ops.disc_head (csrc/disc_head.hip), which reads the weight transposed in place.
         if x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last):
+            if DISC_HEAD and ops.disc_head_supported(x, self.adv_layer):
+                return ops.disc_head(x, self.adv_layer.weight, self.adv_layer.bias)
             n, c, h, w = x.shape
             wp = self.adv_layer.weight.view(-1, c, h, w).permute(0, 2, 3, 1).reshape(self.adv_layer.out_features, -1)
             return F.linear(x.permute(0, 2, 3, 1).reshape(n, -1), wp, self.adv_layer.bias)

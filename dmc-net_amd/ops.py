@@ -6,7 +6,7 @@ import torch
 from . import _lib
 
 __all__ = ["gen_tiny", "flow_mse", "flow_loss", "gen_tiny_loss", "FLOW_LOSS_KINDS", "consensus_ce", "disc_tail", "bn_act", "bn_act_supported", "prepare_inputs",
-           "u8_frames_buffer", "conv_nhwc", "conv_nhwc_supported", "disc_block", "disc_block_supported"]
+           "u8_frames_buffer", "conv_nhwc", "conv_nhwc_supported", "disc_block", "disc_block_supported", "disc_head", "disc_head_supported"]
 
 
 class EventProbe(object):
@@ -1799,7 +1799,8 @@ class _DiscBlock(torch.autograd.Function):
     the convolution epilogue applies bias / LeakyReLU / mask and reduces the BatchNorm statistics, one
     streaming pass normalises; the backward folds the BatchNorm backward, the mask and the LeakyReLU
     derivative into one pass and feeds the matrix-core data / weight gradients.
-    ``first`` = the 2-channel NCHW input block (direct kernels, disc_first.hip)."""
+    ``first`` = 1 / True: the 2-channel NCHW input block (direct kernels, disc_first.hip); 2: Discriminator4's 8 -> 16 block on
+    NHWC (direct kernels, disc_c8.hip: the same epilogue and statistic partials as the matrix-core route); 0: conv_nhwc.hip."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, keep, gamma, beta, running_mean, running_var, stride, training, eps,
@@ -1808,7 +1809,7 @@ class _DiscBlock(torch.autograd.Function):
         _need_cuda(x, weight, bias, keep, gamma, beta)
         use_bn = gamma is not None
         cout = weight.shape[0]
-        if first:
+        if first == 1:
             x = x.contiguous()
             m, _, h, w = x.shape
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -1820,6 +1821,17 @@ class _DiscBlock(torch.autograd.Function):
             part, nblk = None, 0
             if use_bn:
                 raise NotImplementedError("the 2-channel first block has no BatchNorm in any discriminator")
+        elif first == 2:
+            x, wq = _as_cl(x), _as_cl(weight)
+            m, _, h, w = x.shape
+            z = torch.empty((m, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device, memory_format=_CL)
+            part, nblk = None, 0
+            if use_bn and training:
+                nblk = lib.dmc_disc_c8_stat_blocks(m, h, w)
+                part = torch.empty((nblk, cout, 2), dtype=torch.float64, device=x.device)
+            with _span("disc_c8_fwd"):
+                _lib.check(lib.dmc_disc_c8_fwd(_lib.ptr(x), _lib.ptr(wq), _lib.ptr(bias), _lib.ptr(keep), _lib.ptr(z), _lib.ptr(part),
+                                               nblk, m, h, w, 1, _stream()), "dmc_disc_c8_fwd")
         else:
             x, wq = _as_cl(x), _as_cl(weight)
             with _span("disc_conv_fwd"):
@@ -1845,7 +1857,7 @@ class _DiscBlock(torch.autograd.Function):
                                                   _lib.ptr(stats), None, None, m_rows, cout, 0, 0, float(eps),
                                                   float(momentum), _stream()), "dmc_bn_act_fwd")
         ctx.save_for_backward(x, weight, z, keep, gamma, beta, stats)
-        ctx.cfg = (int(stride), bool(training), bool(first), use_bn, bias is not None)
+        ctx.cfg = (int(stride), bool(training), int(first), use_bn, bias is not None)
         return y
 
     @staticmethod
@@ -1870,7 +1882,22 @@ class _DiscBlock(torch.autograd.Function):
                        "dmc_bn_bwd_act_nhwc")
         dx = dw = db = None
         want_w = ctx.needs_input_grad[1]
-        if first:
+        if first == 2:
+            wq = _as_cl(weight)
+            mm, _, h, w = x.shape
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x)
+                with _span("disc_c8_dgrad"):
+                    _lib.check(lib.dmc_disc_c8_dgrad(_lib.ptr(g), _lib.ptr(wq), _lib.ptr(dx), mm, h, w, _stream()), "dmc_disc_c8_dgrad")
+            if want_w:
+                dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device, memory_format=_CL)
+                db = torch.empty(cout, dtype=torch.float32, device=x.device) if has_bias else None
+                work = _floats(lib.dmc_disc_c8_wgrad_bytes(mm, h, w), x.device)
+                with _span("disc_c8_wgrad"):
+                    _lib.check(lib.dmc_disc_c8_wgrad(_lib.ptr(x), _lib.ptr(g), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(work), mm, h, w,
+                                                     _stream()), "dmc_disc_c8_wgrad")
+                dw = _grad_like(dw, weight)
+        elif first:
             wq = weight.contiguous()
             mm, _, h, w = x.shape
             if ctx.needs_input_grad[0]:
@@ -1904,8 +1931,21 @@ class _DiscBlock(torch.autograd.Function):
         return dx, dw, db, None, dgamma, dbeta, None, None, None, None, None, None, None
 
 
-def disc_block_supported(x, conv, first):
-    """True if the HIP discriminator-block path handles this convolution (else the stock ops run)."""
+def _disc_c8_supported(x, conv):
+    """The 8 -> 16, stride-2 block of Discriminator4 on csrc/disc_c8.hip: fp32 weights and bias on the device, a shape that
+    dmc_disc_c8_supported accepts (even H and W)."""
+    if conv.in_channels != 8 or conv.out_channels != 16 or conv.stride != (2, 2) or conv.padding_mode != "zeros":
+        return False
+    if not (conv.weight.is_cuda and conv.weight.dtype == torch.float32):
+        return False
+    n, cin, h, w = x.shape
+    lib = _lib.load()
+    return cin == 8 and bool(lib.dmc_disc_c8_supported(n, h, w)) and bool(lib.dmc_bn_act_supported(1, 16))
+
+
+def disc_block_supported(x, conv, first, c8=False):
+    """True if the HIP discriminator-block path handles this convolution (else the stock ops run).  ``c8``: also count the
+    8 -> 16 route of csrc/disc_c8.hip (the caller's switch, model.DISC_C8)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     if conv.kernel_size != (3, 3) or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1:
@@ -1915,22 +1955,84 @@ def disc_block_supported(x, conv, first):
             bool(_lib.load().dmc_disc_first_supported(conv.out_channels))
     if conv.stride not in ((1, 1), (2, 2)):
         return False
+    if c8 and _disc_c8_supported(x, conv):
+        return True
     return conv_nhwc_supported(x, conv.weight, conv.stride[0], 1) and \
         bool(_lib.load().dmc_bn_act_supported(1, conv.out_channels))
 
 
-def disc_block(x, conv, keep, bn, training, first=False):
+def disc_block(x, conv, keep, bn, training, first=False, c8=False):
     """x -> BN(keep * LeakyReLU_0.2(conv(x))) (BN optional) through the fused NHWC path.  ``x`` is the
-    NCHW 2-channel cue for ``first`` blocks, a channels_last activation otherwise."""
+    NCHW 2-channel cue for ``first`` blocks, a channels_last activation otherwise.  ``c8``: the 8 -> 16 block takes
+    csrc/disc_c8.hip (as disc_block_supported was asked)."""
     if bn is not None and training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     if keep is not None:
         keep = keep.contiguous()
+    first = 1 if first else (2 if c8 and _disc_c8_supported(x, conv) else 0)
     if bn is None:
         return _DiscBlock.apply(x, conv.weight, conv.bias, keep, None, None, None, None, conv.stride[0], training,
                                 0.0, 0.0, first)
     return _DiscBlock.apply(x, conv.weight, conv.bias, keep, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                             conv.stride[0], training, bn.eps, bn.momentum if bn.momentum is not None else 0.1, first)
+
+
+class _DiscHead(torch.autograd.Function):
+    """adv_layer = Linear(C * H * W -> 2) of a discriminator (code/dmcnet_GAN/model.py:290,297-298) on the channels_last activation
+    the blocks leave, csrc/disc_head.hip: the weight stays in the reference's (c, h, w) column order, nothing is permuted or copied.
+    The backward produces only what is asked for: with the discriminator's parameters as constants (the G step) it is one
+    streaming write of dx."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        lib = _lib.load()
+        _need_cuda(x, weight, bias)
+        x, weight, bias = _as_cl(x), weight.contiguous(), bias.contiguous()
+        m, c, h, w = x.shape
+        out = torch.empty((m, 2), dtype=torch.float32, device=x.device)
+        with _span("disc_head_fwd"):
+            _lib.check(lib.dmc_disc_head_fwd(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out), m, c, h, w, _stream()),
+                       "dmc_disc_head_fwd")
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, dv):
+        lib = _lib.load()
+        x, weight = ctx.saved_tensors
+        m, c, h, w = x.shape
+        dv = dv.contiguous()
+        want_x, want_w, want_b = ctx.needs_input_grad
+        if not (want_x or want_w or want_b):
+            return None, None, None
+        dx = torch.empty_like(x) if want_x else None
+        dw = torch.empty_like(weight) if want_w else None
+        db = torch.empty(2, dtype=torch.float32, device=x.device) if want_b else None
+        work = _floats(lib.dmc_disc_head_bwd_bytes(m, c, h, w), x.device) if want_w else None
+        with _span("disc_head_bwd"):
+            _lib.check(lib.dmc_disc_head_bwd(_lib.ptr(x) if want_w else None, _lib.ptr(weight) if want_x else None, _lib.ptr(dv),
+                                             _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(work), m, c, h, w, _stream()),
+                       "dmc_disc_head_bwd")
+        return dx, dw, db
+
+
+def disc_head_supported(x, linear):
+    """True if ``ops.disc_head`` serves ``linear`` (an nn.Linear(C * H * W, 2) with a bias) on the 4-D activation ``x``: fp32 on the
+    GPU, channels_last memory, a shape that dmc_disc_head_supported accepts (C a multiple of 16, fewer than 2^31 elements)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _is_cl(x)):
+        return False
+    wt, b = linear.weight, linear.bias
+    if b is None or not (wt.is_cuda and wt.dtype == torch.float32 and b.dtype == torch.float32):
+        return False
+    m, c, h, w = x.shape
+    if tuple(wt.shape) != (2, c * h * w) or m == 0:
+        return False
+    return bool(_lib.load().dmc_disc_head_supported(m, c, h, w))
+
+
+def disc_head(x, weight, bias):
+    """validity [M, 2] = flatten_(c,h,w)(x) @ weight.T + bias for the channels_last activation ``x`` [M, C, H, W]."""
+    return _DiscHead.apply(x, weight, bias)
 
 
 _STD = (0.229, 0.224, 0.225)

@@ -1105,6 +1105,55 @@ int dmc_ef_layer_dgrad(float* G, const float* w, int N, int H, int W, int CT, in
 int dmc_ef_first_bwd(const float* G, const float* x_nchw, const unsigned short* signs, const float* feat, float* dw_mv, float* db_mv,
                      float* dw_r, float* db_r, void* workspace, int N, int H, int W, int CT, int stack, dmc_stream_t stream);
 
+/* ---- Discriminator4's 8 -> 16 block (disc_c8.hip) ---------------------------------------------------------------
+ * Replaces: the Conv2d(8, 16, 3, stride 2, padding 1) of `discriminator_block(8, 16)`, code/dmcnet_GAN/model.py:254-265 as
+ *           instantiated at :369-385, with its LeakyReLU(0.2) and Dropout2d keep mask, and its autograd.
+ * Layouts:  x [N][H][W][8], z and g [N][OH][OW][16] fp32 NHWC (channels_last memory), OH = (H - 1) / 2 + 1, OW alike; w and dw OHWI
+ *           [16][3][3][8] (the channels_last memory of the PyTorch weight).
+ * dmc_disc_c8_supported: even H and W (odd sizes are refused), every tensor below 2^31 bytes.
+ * fwd:   z = conv(x, w) [+ bias] [LeakyReLU(0.2) if act == 1] [* keep[n][co], the [N][16] Dropout2d mask already divided by 1 - p] --
+ *        the epilogue of dmc_conv_nhwc_fwd -- and, if stat_partials != NULL, the per-channel (sum, sum of squares) of z per
+ *        workgroup in fp64, [stat_blocks = dmc_disc_c8_stat_blocks()][16][2], which dmc_conv_nhwc_stats_final() consumes as they
+ *        are; another stat_blocks is refused, nothing is written.
+ * dgrad: dx [N][H][W][8] = conv_transpose(g, w); every element is written.
+ * wgrad: dw = sum over output pixels, db [16] (nullable) = the channel sums of g: partial sums over runs of 512 consecutive
+ *        output pixels ([runs][1168] floats in the workspace of dmc_disc_c8_wgrad_bytes(), whose contents on entry do not matter),
+ *        added in run order.
+ * Plain fp32 fmaf in a fixed order (72 products per output), no atomics: results are bit-identical from run to run.  The caller
+ * owns every buffer; nothing allocates or synchronises; inputs are read only.
+ * DMC_E_INVALID before any launch (nothing written): a NULL required pointer (bias, keep, stat_partials and db are optional), an
+ * unsupported shape, a stat_blocks that is not the grid's. */
+int dmc_disc_c8_supported(int N, int H, int W);
+int dmc_disc_c8_stat_blocks(int N, int H, int W);
+int dmc_disc_c8_fwd(const float* x, const float* w, const float* bias, const float* keep, float* z, double* stat_partials,
+                    int stat_blocks, int N, int H, int W, int act, dmc_stream_t stream);
+int dmc_disc_c8_dgrad(const float* g, const float* w, float* dx, int N, int H, int W, dmc_stream_t stream);
+size_t dmc_disc_c8_wgrad_bytes(int N, int H, int W);
+int dmc_disc_c8_wgrad(const float* x, const float* g, float* dw, float* db, void* workspace, int N, int H, int W,
+                      dmc_stream_t stream);
+
+/* ---- The discriminators' head on the NHWC activation (disc_head.hip) --------------------------------------------
+ * Replaces: adv_layer = nn.Linear(C * H * W, 2) on `out.view(out.shape[0], -1)`, code/dmcnet_GAN/model.py:290,297-298, and its
+ *           autograd, without the NHWC -> NCHW copy of the activation and without a permuted copy of the weight.
+ * Layouts:  x and dx [M][H][W][C] fp32 (channels_last memory); weight and dweight [2][C * H * W] in the reference's (c, h, w)
+ *           column order; bias, dbias [2]; validity, dvalidity [M][2].
+ * dmc_disc_head_supported: C a multiple of 16, M * C * H * W < 2^31.
+ * fwd: validity[m][j] = bias[j] + sum x[m][h][w][c] * weight[j][c * H * W + h * W + w], one launch, one workgroup per frame: fp32
+ *      fmaf sums per lane, added over lanes and waves in a fixed order, bias last.
+ * bwd: dx = dvalidity[m][0] * weight[0] + dvalidity[m][1] * weight[1]; dweight = sum over the frames of dvalidity[m][j] * x[m];
+ *      dbias = sum over the frames of dvalidity.  Each of dx, dweight, dbias may be NULL (not all three): a dx-only call reads
+ *      neither x nor the workspace (both may be NULL), a call without dx does not read weight (may be NULL).  dweight is summed
+ *      over slices of 16 frames ([slices][2][C * H * W] floats in the workspace of dmc_disc_head_bwd_bytes(), whose contents on
+ *      entry do not matter) and the slices in order; dbias in a fixed order.
+ * No atomics: results are bit-identical from run to run.  The caller owns every buffer; nothing allocates or synchronises; inputs
+ * are read only.  DMC_E_INVALID before any launch (nothing written): a NULL required pointer, an unsupported shape. */
+int dmc_disc_head_supported(int M, int C, int H, int W);
+int dmc_disc_head_fwd(const float* x, const float* weight, const float* bias, float* validity, int M, int C, int H, int W,
+                      dmc_stream_t stream);
+size_t dmc_disc_head_bwd_bytes(int M, int C, int H, int W);
+int dmc_disc_head_bwd(const float* x, const float* weight, const float* dvalidity, float* dx, float* dweight, float* dbias,
+                      void* workspace, int M, int C, int H, int W, dmc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
